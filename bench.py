@@ -2,7 +2,7 @@
 """Throughput of the ZeST-NeRF rendering hot path on MI355X: rendered rays/s.
 
     python bench.py [--gpus N --steps K --warmup W] [--workload NAME] [--mode bf16|f16|f16x3]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 A step is one `renderer.rendering(...)` call (the drop-in boundary) over one batch of
 synthetic rays through the fused HIP renderer, inputs resident in HBM.  Default workload
@@ -14,16 +14,20 @@ from rank 0 before the timed region), rank g renders the g-th contiguous block o
 pixels are all-gathered over RCCL inside the timed region (weak scaling: the batch is --gpus times the workload's
 rays, per-GPU work fixed; --scaling strong splits the workload's own rays over the GPUs, e.g. configs[3]:
 4096 x 192 over 8).
-At N = 1 the JSON also carries `modes`: the fp16 and the fp32-tolerance (split fp16) runs of the
-same kernel on the same workload.
-
-Prints ONE JSON line: metric/value/unit..., plus
+Prints ONE JSON line: metric/value/unit/ms_per_step... of the K timed steps.  A plain run does
+nothing else; --full adds the measurements that take runs of their own:
   roofline:     MFMA bound for the fused kernel - algorithmic MLP FLOPs per launch / average
                 kernel time from HIP events on the launch stream, against 2.5 PFLOP/s
-                (dense bf16, /opt/skills/guides/MI355X_MICROARCH.md)
-  cpu_baseline: the CPU oracle (oracle/zest_oracle.py: the reference's op sequence in
-                PyTorch-CPU fp32) timed on this box's host cores on a bounded sample of the
-                same workload (rank 0, N = 1 only).
+                (dense bf16, MI355X_MICROARCH.md)
+  modes:        (N = 1, unless --no-modes) the other operand types of the same kernel on the
+                same workload: fp16 and the fp32-tolerance (split fp16) runs
+  cpu_baseline: (N = 1, unless --no-cpu-baseline) the CPU oracle (oracle/zest_oracle.py: the
+                reference's op sequence in PyTorch-CPU fp32) timed on the host cores on a bounded
+                sample of the same workload; `psnr` compares the build's colours with it.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's rendering() result: one
+DIR/<key>.npy per tensor, float32) for output-for-output comparison of two builds; the inputs
+are generated from a fixed seed, so they are the same in every run with the same arguments.
 """
 import argparse
 import json
@@ -234,6 +238,23 @@ def launch_ranks(a, argv):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(ret, out_dir, seed=0):
+    """Every tensor of a rendering() result as out_dir/<key>.npy in float32.  If they hold more than
+    DUMP_BYTES together, each is cut to the same fixed, seeded sample share of its elements (flattened)."""
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in ret.items() if torch.is_tensor(v)}
+    total = 4 * sum(x.size for x in arrs.values())
+    budget = DUMP_BYTES - (1 << 20)                    # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in sorted(arrs.items()):
+        if total > budget:
+            idx = np.random.default_rng(seed).choice(x.size, x.size * budget // total, replace=False)
+            x = x.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+
+
 def _dry_maps(rank, R, step):
     """Stand-in for the rendered maps of one step in --dry runs (CPU, no HIP): row r of rank g holds
     its global ray index, so the gathered tensor can be checked."""
@@ -255,12 +276,18 @@ def main():
                     help="weak: every GPU renders the workload's ray count; strong: the ray count is split over the GPUs")
     ap.add_argument("--gather", default="image", choices=["image", "step"],
                     help="N>1: all-gather the rendered maps once per image (default) or per call")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the extra f16 / f16x3 lines of the JSON")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the other operand types and the CPU baseline (runs of their own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and PSNR")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the extra f16 / f16x3 lines of the JSON")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--dry", action="store_true",
                     help="CPU rehearsal of the launcher + collective (gloo, stand-in maps, no HIP): tests only")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(a, sys.argv[1:]))
@@ -319,7 +346,7 @@ def main():
     # of IMAGE_PIXELS rays (--gather image, default): every rank keeps its chunks and pushes them
     # in one message, so the latency-bound collective is paid once per image, not per chunk.
     per_image = max(1, IMAGE_PIXELS // max(1, world * d.R))
-    chunks, gathered, n_step = [], [], [0]
+    chunks, gathered, n_step, last = [], [], [0], [None]
 
     def flush():
         if chunks:
@@ -339,6 +366,7 @@ def main():
             chunks.append(ret["zest_packed_maps"])
             if a.gather == "step" or len(chunks) >= per_image:
                 flush()
+        last[0] = ret
         return ret
 
     def fence():
@@ -378,6 +406,8 @@ def main():
         return float(np.median([x.elapsed_time(y) for x, y in evs]))      # median: one pre-empted launch must not skew it
 
     el = timed_loop()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(last[0], a.dump_outputs)
     if a.dry:
         # every gathered tensor: `world` equal blocks in rank order, each a run of whole chunks whose
         # rows carry the global ray indices rank * R .. rank * R + R - 1 in order
@@ -394,11 +424,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    k_ms = kernel_ms()
+    k_ms = kernel_ms() if a.full else None
     if rank == 0:
-        flops, fps = flops_per_ray_batch(d)
-        peak = MODES[a.mode][2]
-        ach = flops / (k_ms * 1e-3) / 1e12
         coll = "none"
         if world > 1:
             coll = ("all_gather(packed per-ray maps) per rendering call" if a.gather == "step" else
@@ -414,15 +441,19 @@ def main():
                        "path": "renderer.rendering -> zest_render_fused_fwd", "collective": coll,
                        "ranks": dist.get_world_size() if dist is not None else 1,
                        "backend": ("rccl" if dist is not None else "none")},
-            "roofline": {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
-                         "frac": ach / peak, "traffic": pmc_traffic(a.workload, a.mode),
-                         "kernel": "fused_blocks_kernel (one launch: a range of whole rays per workgroup, rays finished in the kernel)",
-                         "kernel_ms": k_ms, "flop_per_sample": fps,
-                         "note": "achieved = algorithmic MLP FLOPs of one launch / HIP-event time of the "
-                                 "launch on its stream; traffic = HBM bytes per launch from the "
-                                 "rocprofv3 PMC passes archived in profiles/ (null if none for this workload)"},
         }
-    if world == 1 and not a.no_modes:
+        if a.full:
+            flops, fps = flops_per_ray_batch(d)
+            peak = MODES[a.mode][2]
+            ach = flops / (k_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s",
+                               "frac": ach / peak, "traffic": pmc_traffic(a.workload, a.mode),
+                               "kernel": "fused_blocks_kernel (one launch: a range of whole rays per workgroup, rays finished in the kernel)",
+                               "kernel_ms": k_ms, "flop_per_sample": fps,
+                               "note": "achieved = algorithmic MLP FLOPs of one launch / HIP-event time of the "
+                                       "launch on its stream; traffic = HBM bytes per launch from the "
+                                       "rocprofv3 PMC passes archived in profiles/ (null if none for this workload)"}
+    if a.full and world == 1 and not a.no_modes:
         # the other operand types of the same kernel on the same workload: fp16 (configs[4]) and the
         # fp32-tolerance mode (split fp16, north-star 1e-4 abs / 1e-3 rel), same protocol
         modes = {}
@@ -446,7 +477,7 @@ def main():
         set_mode(d, a.mode)
         out["modes"] = modes
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             with torch.no_grad():
                 build_ret = render_step(d)
             torch.cuda.synchronize()

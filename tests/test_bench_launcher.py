@@ -2,13 +2,15 @@
 torch.distributed.run) when called from a plain shell, refuses a launcher that started a different
 number of ranks, and keeps the all-gather of the rendered maps inside the timed region.  `--dry`
 swaps the HIP render for stand-in maps and RCCL for gloo so the launcher, the rendezvous, the
-sharding arithmetic and the collective run here."""
+sharding arithmetic and the collective run here, and `--dump-outputs` writes the last timed step's arrays."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -53,13 +55,68 @@ def test_rank_count_mismatch_is_an_error():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_dry_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the arrays of the LAST timed step (stand-in maps carry their step number) as float32,
+    the same in every run with the same arguments."""
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / str(i)
+        r = _run(["--dry", "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out_dir)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert _json_line(r)["steps"] == 3
+        assert sorted(os.listdir(out_dir)) == ["zest_packed_maps.npy"]
+        dumps.append(np.load(out_dir / "zest_packed_maps.npy"))
+    got = dumps[0]
+    assert got.dtype == np.float32 and got.shape == (1024, 16)
+    want = np.arange(1024, dtype=np.float32)[:, None].repeat(16, 1) + np.float32(0.001 * 4)   # step 4 = 2 + 3 - 1
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(dumps[1], got)
+
+
+def test_dump_outputs_samples_past_the_size_cap(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 << 20)
+    ret = {"a": torch.arange(1 << 20, dtype=torch.float32), "b": torch.ones(2, 1 << 19, dtype=torch.float64), "n": 3}
+    bench.dump_outputs(ret, str(tmp_path / "x"))
+    bench.dump_outputs(ret, str(tmp_path / "y"))
+    a, b = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert a.dtype == b.dtype == np.float32 and a.size == b.size == (2 << 20) // 8
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= 3 << 20
+    assert (np.diff(a) > 0).all() and (b == 1).all()                 # sorted sample of the flattened elements
+    np.testing.assert_array_equal(np.load(tmp_path / "y" / "a.npy"), a)
+
+
+def test_steps_must_be_positive():
+    r = _run(["--dry", "--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dump_on_the_gpu(tmp_path):
+    """A plain run (no --full) on one GPU: the headline keys only, none of the --full measurements, and the rendered
+    maps of its last timed step in --dump-outputs."""
+    r = _run(["--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _json_line(r)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in out, k
+    assert out["steps"] == 5 and out["dtype"] == "bf16" and out["value"] > 1e5 and out["ms_per_step"] > 0
+    assert not {"roofline", "modes", "cpu_baseline", "psnr"} & set(out)
+    maps = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"rgb_map", "depth_map", "acc_map", "zest_packed_maps"} <= set(maps)
+    assert maps["rgb_map"].shape == (1, 1024, 3) and maps["zest_packed_maps"].shape[0] == 1024
+    for k, x in maps.items():
+        assert x.dtype == np.float32 and np.isfinite(x).all(), k
+    np.testing.assert_array_equal(maps["rgb_map"][0], maps["zest_packed_maps"][:, 0:3])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["bf16", "f16x3"])
 def test_bench_json_line_on_the_gpu(mode):
-    """The real (non --dry) bench on one GPU, short: ONE JSON line with the contract's keys, the roofline object and
-    the other operand types in `modes` - also when the headline mode is f16x3 (the line used to die on a KeyError
-    after all the timing was done)."""
-    r = _run(["--steps", "5", "--warmup", "2", "--mode", mode, "--no-cpu-baseline"], timeout=600)
+    """The real (non --dry) bench on one GPU with --full, short: ONE JSON line with the contract's keys, the roofline
+    object and the other operand types in `modes` - also when the headline mode is f16x3 (the line used to die on a
+    KeyError after all the timing was done)."""
+    r = _run(["--full", "--steps", "5", "--warmup", "2", "--mode", mode, "--no-cpu-baseline"], timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _json_line(r)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",

@@ -415,11 +415,11 @@ def sample_rays(xs, ys, K_tgt, c2w_tgt, w2c_ref, K_ref, near_tgt, far_tgt, near_
 
 
 # ----------------------------------------------------- plane sweep (8(f) row 3)
-# Pinning: the reference's homo_warp builds its pixel grid with kornia.create_meshgrid, which
-# is not installed here, so only its sampling half (a given src_grid -> F.grid_sample, zero
-# padding, align_corners; utils.py:91-98) is pinned by a reference-generated fixture
-# (tests/golden/homo_warp.npz).  plane_grid and volume_cost below restate utils.py:57-89 and
-# networks.py:1077-1140 from the source text: PARITY UNPINNED for those two.
+# Pinning: tests/golden/volume_cost_*.npz hold the output of the reference's own homo_warp (grid
+# construction included, run with a stand-in for kornia.utils.create_meshgrid, which is not installed)
+# and MVSNet.build_volume_cost, with the reference's autograd gradient; plane_grid, grid_warp and
+# volume_cost below reproduce them bit for bit (tests/test_oracle_golden.py).  The reference
+# hard-codes 9 + 32 channels, so the fixtures are V = 3; other view counts follow from the same code.
 def plane_grid(proj, depth, H, W, pad=0):
     """proj [3,4] = src_proj @ ref_proj_inv, depth [D] -> normalised source positions
     [D, H+2pad, W+2pad, 2] of every reference pixel (x - pad, y - pad) on every depth plane.

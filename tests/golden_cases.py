@@ -152,6 +152,11 @@ def cost_inputs(seed, V=3, H=18, W=24, D=6, pad=2, spread=0.35):
     return dict(feats=feats, imgs=imgs, proj_mats=proj_mats, depth_values=depth_values, pad=pad)
 
 
+def cost_grad_weights(seed, V, D, Hp, Wp):
+    """Loss weights [3V+32, D, Hp, Wp] of the plane-sweep gradient tests: loss = sum(gw * img_feat)."""
+    return zs.rng(seed + 500).standard_normal((3 * V + 32, D, Hp, Wp)).astype(np.float32)
+
+
 def builder_net_inputs(seed, D=16, H=16, W=24):
     """Seeded state dicts (reference key names) and inputs for the two convolution stacks of the volume builder:
     CostRegNet(32 + 9) on a [1,41,D,H,W] cost volume and FeatureNet on three [3,4H,4W]... images.  The keys and shapes come
@@ -248,6 +253,16 @@ CASES = {
                               variable_patches=True, scale_anneal=0.0025, step=3000),      # GRAF: N_rays = patch_size^2
     "homo_warp": dict(kind="homo_warp", seed=63, pad=3),
     "builder_nets": dict(kind="builder_nets", seed=64),
+    # The reference's OWN plane sweep (utils.homo_warp grid construction + MVSNet.build_volume_cost, V = 3, 32
+    # feature channels) on cost_inputs().  Stored: img_feat [41,D,Hp,Wp], in_masks [3,D,Hp,Wp], grid_1 / grid_2
+    # [D,Hp,Wp,2], warped_1 [32,D,Hp,Wp] (where `warped`), g_feats [3,32,H,W] = d sum(gw * variance) / d feats by the
+    # reference's autograd.  Channels 0-2 of the padding ring, which the reference allocates and never writes, are
+    # stored as 0 and are not defined by the reference.  No grid component of any case lies within 2e-5 of +-1, so a
+    # grid within 2e-5 of the stored one gives the stored masks exactly (asserted by the generator).
+    "volume_cost_plain": dict(kind="volume_cost", seed=81, H=12, W=16, D=8, pad=0, warped=True),    # 1536 voxels = 24 waves
+    "volume_cost_ragged": dict(kind="volume_cost", seed=82, H=17, W=23, D=3, pad=3, warped=False),   # 2001 = 31 * 64 + 17
+    "volume_cost_ring24": dict(kind="volume_cost", seed=83, H=10, W=12, D=2, pad=24, warped=True),     # ring larger than the image
+    "volume_cost_wide": dict(kind="volume_cost", seed=84, H=12, W=16, D=6, pad=2, spread=2.5, warped=False),
     "loss_side": dict(kind="loss_side", seed=71),
     "render_static_mvs": dict(kind="render", seed=31, use_mvs=True),
     "render_static_nomvs": dict(kind="render", seed=32, use_mvs=False),
@@ -313,6 +328,8 @@ def build(case):
         return loss_inputs(c["seed"], jitter=c.get("jitter", False))
     if k == "homo_warp":
         return cost_inputs(c["seed"], V=c.get("V", 3), pad=c["pad"])
+    if k == "volume_cost":
+        return cost_inputs(c["seed"], V=3, H=c["H"], W=c["W"], D=c["D"], pad=c["pad"], spread=c.get("spread", 0.35))
     if k == "builder_nets":
         return builder_net_inputs(c["seed"])
     if k == "rays":

@@ -154,7 +154,28 @@ def run(case, dtype=torch.float32, explicit=True):
             out = oracle_render(c, inp, dtype, explicit)
     if k == "loss_side":
         out = loss_side(inp, dtype)
+    if k == "volume_cost":
+        out = volume_cost(c, inp, dtype)
     return {kk: (v.double().numpy() if v is not None else None) for kk, v in out.items()}
+
+
+def volume_cost(c, inp, dtype=torch.float32):
+    """Oracle plane sweep with the fixture's key names: both outputs of zo.volume_cost, the sampling grids and the
+    warped features of the source views, and the autograd gradient of sum(gw * variance) with respect to feats."""
+    t = lambda k: T(inp[k], dtype)[0]
+    pad = inp["pad"]
+    feats = t("feats").requires_grad_(True)
+    V, _, H, W = feats.shape
+    D = inp["depth_values"].shape[1]
+    img_feat, masks = zo.volume_cost(t("imgs"), feats, t("proj_mats"), t("depth_values"), pad)
+    gw = T(gc.cost_grad_weights(c["seed"], V, D, H + 2 * pad, W + 2 * pad), dtype)
+    (img_feat[-32:] * gw[-32:]).sum().backward()
+    out = dict(img_feat=img_feat.detach(), in_masks=masks, g_feats=feats.grad)
+    with torch.no_grad():
+        for i in range(1, V):
+            out["grid_%d" % i] = zo.plane_grid(t("proj_mats")[i], t("depth_values"), H, W, pad)
+        out["warped_1"] = zo.grid_warp(feats.detach()[1], out["grid_1"])
+    return out
 
 
 def loss_side(inp, dtype=torch.float32):

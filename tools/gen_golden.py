@@ -4,7 +4,8 @@
 Runs only in the build container (needs /root/reference).  The reference modules
 `renderer`, `utils`, `networks` import four packages that are absent here and are
 not used on the rendering path (cv2, torchvision, kornia, inplace_abn; SURVEY.md
-section 8(c)); empty placeholder modules are registered for them before import.
+section 8(c)); placeholder modules are registered for them before import, empty but for
+a stand-in for kornia.utils.create_meshgrid, the one function the plane sweep needs.
 Inputs and weights come from the build's own seeded generator
 (tests/golden_cases.py + zest-nerf_amd/zest_synth.py); only the reference's OUTPUTS
 are written.  Nothing from the reference's source is copied.
@@ -28,6 +29,18 @@ import golden_cases as gc  # noqa: E402
 REF = "/root/reference"
 
 
+def create_meshgrid(height, width, normalized_coordinates=True, device=None, dtype=torch.float32):
+    """Stand-in for kornia.utils.create_meshgrid (kornia is not installed), written from kornia's documented
+    contract, not from the reference: a float32 tensor [1, height, width, 2] whose last axis is (x, y), with x
+    varying fastest; integer pixel coordinates 0..width-1 / 0..height-1 when normalized_coordinates is False,
+    [-1, 1] on both axes otherwise."""
+    xs = torch.linspace(0, width - 1, width, device=device, dtype=dtype)
+    ys = torch.linspace(0, height - 1, height, device=device, dtype=dtype)
+    if normalized_coordinates:
+        xs, ys = (xs / (width - 1) - 0.5) * 2, (ys / (height - 1) - 0.5) * 2
+    return torch.stack([xs[None, :].expand(height, width), ys[:, None].expand(height, width)], -1)[None].contiguous()
+
+
 def _placeholders():
     def mod(name):
         m = types.ModuleType(name)
@@ -39,7 +52,7 @@ def _placeholders():
     tv.utils = mod("torchvision.utils")
     k = mod("kornia")
     k.utils = mod("kornia.utils")
-    k.utils.create_meshgrid = lambda *a, **kw: None   # only homo_warp uses it (off-path)
+    k.utils.create_meshgrid = create_meshgrid         # homo_warp's pixel grid (utils.py binds the name at import)
     abn = mod("inplace_abn")
 
     class InPlaceABN(torch.nn.Module):                # default arg of off-path CNN blocks
@@ -80,7 +93,7 @@ def run_case(ref, name):
     inp = gc.build(name)
     k = c["kind"]
     out = {}
-    with torch.set_grad_enabled(k == "render_grad"):
+    with torch.set_grad_enabled(k == "render_grad"):            # (volume_cost switches autograd on for its gradient)
         if k == "composite":
             z, d = T(inp["z"])[None], T(inp["rays_dir"])[None]
             dists = ref.renderer.depth2dist(z, torch.norm(d, dim=-1, keepdim=True))
@@ -119,6 +132,8 @@ def run_case(ref, name):
             out = run_homo_warp(ref.utils, inp)
         elif k == "builder_nets":
             out = run_builder_nets(ref.networks, inp)
+        elif k == "volume_cost":
+            out = run_volume_cost(ref, c, inp)
         elif k == "rays":
             out = run_rays(ref.utils, c, inp)
         elif k == "render":
@@ -184,9 +199,8 @@ def run_builder_nets(N, inp):
 def run_homo_warp(U, inp):
     """The sampling half of utils.homo_warp (utils.py:91-98): source view 1's feature map and its
     resized image warped with a GIVEN grid.  The grid is an input here (computed by the oracle's
-    plane_grid): the reference's own grid construction needs kornia.create_meshgrid, which is
-    not installed, so that half stays unpinned (oracle/zest_oracle.py).  Also used by the GPU
-    test against our utils.homo_warp."""
+    plane_grid); the reference's own grid construction is pinned by the volume_cost_* cases
+    (run_volume_cost).  Also used by the GPU test against our utils.homo_warp."""
     from oracle import zest_oracle as zo
     pad = inp["pad"]
     feats, imgs = T(inp["feats"]), T(inp["imgs"])
@@ -198,6 +212,64 @@ def run_homo_warp(U, inp):
     img_lr = torch.nn.functional.interpolate(imgs[0], (H, W), mode="bilinear", align_corners=False)[1:2]
     img_warped, _ = U.homo_warp(img_lr, T(inp["proj_mats"])[:, 1], T(inp["depth_values"]), src_grid=grid, pad=pad)
     return dict(warped=warped[0].numpy(), img_warped=img_warped[0].numpy())
+
+
+def run_volume_cost(ref, c, inp):
+    """The reference's own plane sweep: MVSNet.build_volume_cost (networks.py:1077-1140) as an unbound call - the
+    method reads nothing of `self` but .training, and the constructor needs InPlaceABN - in both branches (in place
+    / out of place), utils.homo_warp (utils.py:49-99) building its own grid, and the reference's autograd for
+    d sum(gw * variance) / d feats.  img_feat comes from torch.empty and channels 0-2 are never written on the
+    padding ring: exactly those entries are overwritten with 0 before saving.  Asserts the conditions that let the
+    tests compare masks exactly (see golden_cases.CASES)."""
+    pad, seed = inp["pad"], c["seed"]
+    imgs, feats, proj, depth = T(inp["imgs"]), T(inp["feats"]), T(inp["proj_mats"]), T(inp["depth_values"])
+    H, W = feats.shape[-2:]
+    D, Hp, Wp = depth.shape[1], H + 2 * pad, W + 2 * pad
+    ring = torch.ones(Hp, Wp, dtype=torch.bool)
+    ring[pad:H + pad, pad:W + pad] = False
+
+    def sweep(training, f):
+        img_feat, masks = ref.networks.MVSNet.build_volume_cost(SimpleNamespace(training=training), imgs.clone(), f,
+                                                                proj.clone(), depth.clone(), pad=pad)
+        assert tuple(img_feat.shape) == (1, 41, D, Hp, Wp) and tuple(masks.shape) == (1, 3, D, Hp, Wp)
+        return img_feat, masks
+
+    def defined(img_feat):
+        x = img_feat.detach().clone()
+        x[0, :3][:, :, ring] = 0.0
+        return x
+    with torch.no_grad():
+        f_eval, m_eval = sweep(False, feats.clone())
+        f_train, m_train = sweep(True, feats.clone())
+        assert torch.equal(defined(f_eval), defined(f_train)) and torch.equal(m_eval, m_train)
+        out = dict(img_feat=defined(f_eval)[0].numpy(), in_masks=m_eval[0].numpy())
+        for i in (1, 2):
+            warped, grid = ref.utils.homo_warp(feats[:, i].clone(), proj[:, i].clone(), depth.clone(), pad=pad)
+            assert tuple(grid.shape) == (1, D, Wp, Hp, 2)
+            out["grid_%d" % i] = grid.reshape(D, Hp, Wp, 2).numpy().copy()
+            if i == 1 and c.get("warped", False):
+                out["warped_1"] = warped[0].numpy().copy()
+    with torch.enable_grad():
+        f = feats.clone().requires_grad_(True)
+        img_feat, _ = sweep(True, f)
+        gw = T(gc.cost_grad_weights(seed, 3, D, Hp, Wp))
+        (img_feat[0, -32:] * gw[-32:]).sum().backward()
+        out["g_feats"] = f.grad[0].numpy().copy()
+    # conditions on the inputs, so that no test on these cases needs an allowance
+    assert all(np.isfinite(v).all() for v in out.values()), "non-finite output"
+    xs, ys = np.meshgrid(np.arange(Wp, dtype=np.float64) - pad, np.arange(Hp, dtype=np.float64) - pad)
+    for i in (1, 2):
+        P = inp["proj_mats"][0, i].astype(np.float64)
+        z = P[2, 0] * xs[None] + P[2, 1] * ys[None] + P[2, 2] + P[2, 3] / inp["depth_values"][0].astype(np.float64)[:, None, None]
+        assert np.abs(z).min() >= 1e-3, "view %d: |Z| %.3g" % (i, np.abs(z).min())
+        edge = np.abs(np.abs(out["grid_%d" % i].astype(np.float64)) - 1.0).min()
+        assert edge > 2e-5, "view %d: a grid component lies %.3g from +-1" % (i, edge)
+    share = out["in_masks"][1:].mean()
+    assert 0.02 < share < 0.98, share
+    if c.get("spread", 0) > 1:
+        assert (out["in_masks"].sum(0) == 1).any(), "no voxel with the reference view alone"
+        assert min(out["in_masks"][1].mean(), out["in_masks"][2].mean()) < 0.10
+    return out
 
 
 def run_render_grad(ref, c, sc):

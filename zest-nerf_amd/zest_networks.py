@@ -333,10 +333,11 @@ class MVSNeRF(nn.Module):
 # InPlaceABN (inplace_abn, a CUDA-only extension that is not installable here): its forward is
 # batch norm followed by leaky ReLU(0.01), and its parameters are weight / bias / running_mean /
 # running_var, so ActivatedBatchNorm keeps the reference's state-dict keys and checkpoints load.
-# Parity: the sampling half of homo_warp is pinned by a reference-generated fixture
-# (tests/golden/homo_warp.npz); the grid construction and build_volume_cost are checked against the
-# oracle's restatement of the source text, and the convolutional stacks cannot be run in the
-# reference without inplace_abn: "parity unpinned" for those.
+# Parity: homo_warp (grid construction and sampling) and build_volume_cost are pinned at V = 3 by
+# reference-generated fixtures (tests/golden/homo_warp.npz, volume_cost_*.npz: forward, masks and the
+# gradient with respect to the features); other view counts, which the reference cannot run, are checked
+# against the oracle.  The wiring of the convolutional stacks is pinned under the stated reading of the
+# norm (builder_nets.npz); InPlaceABN's own arithmetic cannot be run here: "parity unpinned" (DESIGN.md 4b).
 class ActivatedBatchNorm(nn.BatchNorm2d):
     """InPlaceABN substitute: BatchNorm (any spatial rank) + leaky ReLU(0.01)."""
 

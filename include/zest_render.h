@@ -179,8 +179,17 @@ int zest_homo_warp_fwd(const float *src, const float *proj, const float *depth, 
  * zest_conv2d_fwd: the same kernel on a batch of N images [N,H,W,cin] channels-last - Conv2d(cin -> cout, k, stride,
  *   padding k/2, no bias) on act(norm(in)) (pre NULL: on `in` itself - first layer only), the layers of FeatureNet
  *   (reference networks.py:962-1001): 8->8 k3 (3 input channels padded to 8), 8->16 k5/2, 16->16 k3, 16->32 k5/2,
- *   32->32 k3.  w_packed: zest_conv2d_packed_bytes(cin, cout, k, passes) bytes; out, stats, passes as above. */
+ *   32->32 k3.  w_packed: zest_conv2d_packed_bytes(cin, cout, k, passes) bytes; out, stats, passes as above.
+ * zest_costreg_conv_launch_shape: what zest_costreg_conv_fwd / zest_conv2d_fwd launch for an OUTPUT of Do x Ho x Wo
+ *   voxels (2-D: Do = N): *rows_per_wave = output rows of a tile (a tile: that many rows x 16 voxels in x of one
+ *   slice; 4, or 1 where Do Ho ceil(Wo / 16) < 8192), *n_tiles, *n_wg = workgroups (four waves, a tile each; from
+ *   4096 tiles on: 1024 workgroups whose waves walk several tiles) = rows of the statistics table in use.
+ * zest_costreg_deconv_launch_shape: the same for zest_costreg_deconv_fwd on an INPUT of Di x Hi x Wi voxels (a tile:
+ *   16 voxels of one input row and the 2 x 2 x 32 output voxels over them).
+ *   Both: host arithmetic only - the launches compute their shape with the same code; any result pointer may be NULL. */
 int zest_costreg_stat_rows(void);
+int zest_costreg_conv_launch_shape(int Do, int Ho, int Wo, int *rows_per_wave, int *n_tiles, int *n_wg);
+int zest_costreg_deconv_launch_shape(int Di, int Hi, int Wi, int *n_tiles, int *n_wg);
 size_t zest_conv2d_packed_bytes(int cin, int cout, int k, int passes);
 int zest_conv2d_fwd(const float *in, const float *pre, const void *w_packed, int cin, int cout, int k, int stride,
                     int passes, int N, int Hi, int Wi, float *out, double *stats, void *stream);

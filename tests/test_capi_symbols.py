@@ -108,6 +108,42 @@ def test_fused_pass_shape_covers_every_block_once():
             assert rounds <= dense_rounds or not ranges
 
 
+def test_costreg_launch_shapes():
+    """Host arithmetic of the builder's convolution launches (no GPU call; the launches run the same code):
+    convolution, from the OUTPUT extents -> (rows per wave, tiles, workgroups); transposed convolution, from the
+    INPUT extents -> (tiles, workgroups).  Four rows per wave from 8192 rows of 16 voxels on, one below; four waves
+    (a tile each) per workgroup up to 4095 tiles, from 4096 on 1024 workgroups - the rows of the statistics table."""
+    sys.path.insert(0, os.path.join(ROOT, "zest-nerf_amd"))
+    import zest_hip as zh
+    conv, deconv = zh.costreg_conv_launch_shape, zh.costreg_deconv_launch_shape
+    assert zh.costreg_stat_rows() == 1024 + 1
+    # an NSFF image: 128 planes of 120 x 176 and the levels below; three images of 480 x 704 and the levels below
+    assert conv(128, 120, 176) == (4, 128 * 30 * 11, 1024)
+    assert conv(64, 60, 88) == (4, 64 * 15 * 6, 1024)
+    assert conv(32, 30, 44) == (1, 32 * 30 * 3, 720)
+    assert conv(16, 15, 22) == (1, 16 * 15 * 2, 120)
+    assert conv(3, 480, 704) == (4, 3 * 120 * 44, 1024) and conv(3, 240, 352) == (4, 3 * 60 * 22, 990)
+    assert conv(3, 120, 176) == (1, 3 * 120 * 11, 990)
+    assert deconv(16, 15, 22) == (480, 120) and deconv(32, 30, 44) == (2880, 720) and deconv(64, 60, 88) == (23040, 1024)
+    # rows of 16 voxels: 8191 (a prime) | 8192
+    assert conv(8191, 1, 16) == (1, 8191, 1024) and conv(8192, 1, 16) == (4, 8192, 1024)
+    assert conv(1, 8191, 3) == (1, 8191, 1024) and conv(1, 8192, 3) == (4, 2048, 512)
+    assert conv(1, 4095, 32) == (1, 8190, 1024) and conv(1, 4096, 32) == (4, 2048, 512)
+    # tiles: 4092 .. 4097 (one row per wave), 4095 | 4096 (four): the grid never passes the statistics table
+    assert [conv(n, 1, 16)[1:] for n in (4092, 4093, 4095, 4096, 4097)] == \
+        [(4092, 1023), (4093, 1024), (4095, 1024), (4096, 1024), (4097, 1024)]
+    assert conv(4095, 4, 48) == (4, 4095 * 3, 1024) and conv(4095, 4, 9) == (4, 4095, 1024)
+    assert conv(1365, 4, 33) == (4, 4095, 1024) and conv(1024, 4, 64) == (4, 4096, 1024) and conv(1364, 4, 33) == (4, 4092, 1023)
+    assert [deconv(n, 1, 16) for n in (4092, 4095, 4096, 4097)] == [(4092, 1023), (4095, 1024), (4096, 1024), (4097, 1024)]
+    assert deconv(7, 5, 17) == (70, 18) and deconv(1, 1, 1) == (1, 1) and conv(1, 1, 1) == (1, 1, 1)
+    # the ragged ends count as whole tiles
+    assert conv(24, 43, 125) == (4, 24 * 11 * 8, 528) and conv(40, 50, 150) == (4, 5200, 1024) and conv(20, 30, 112) == (1, 4200, 1024)
+    with pytest.raises(RuntimeError, match="zest_costreg_conv_launch_shape"):
+        conv(0, 4, 4)
+    with pytest.raises(RuntimeError, match="zest_costreg_deconv_launch_shape"):
+        deconv(4, -1, 4)
+
+
 def test_train16_size_queries_refuse_other_mlp_shapes():
     """The bf16 training kernels are unrolled for depth 8 / width 256 / skips [4]; the size queries of the C ABI
     (no GPU call) answer 0 with an error text for any other descriptor, also AFTER a default-shape query has

@@ -573,18 +573,39 @@ __global__ __launch_bounds__(256) void costreg_out_kernel(const float4 *__restri
         out[(size_t)c * nvox + i] = leaky(fmaf(va[c], pa[c], pa[8 + c])) + leaky(fmaf(vb[c], pb[c], pb[8 + c]));
 }
 
+// Launch shape of the two MFMA kernels (host arithmetic; zest_costreg_conv_launch_shape / _deconv_launch_shape answer
+// with the same functions the launches use).  A tile is RT output rows x 16 voxels in x of one slice (transposed
+// convolution: one input row x 16 voxels); a workgroup's four waves take a tile each, and from 4096 tiles on the grid
+// stays at kStatRows workgroups (one row of the statistics table each) and a wave walks several tiles.
+struct LaunchShape { int rt, n_xb, n_yg, n_tiles, grid; };
+inline int grid_of_tiles(int n_tiles) { return n_tiles < 4 * kStatRows ? (n_tiles + 3) / 4 : kStatRows; }
+inline LaunchShape conv_launch_shape(int Do, int Ho, int Wo) {
+    LaunchShape s;
+    s.n_xb = (Wo + 15) / 16;
+    const long long rows = (long long)Do * Ho * s.n_xb;
+    // rows per wave: 4 - or 1 on the small levels, so that the tiles still cover the chip.  (8 for the first layer -
+    // fewer strips per output row, 10 / 8 instead of 6 / 4 - does not fit two waves per SIMD: 500 - 800 spilled
+    // registers.)
+    s.rt = rows < 8192 ? 1 : 4;
+    s.n_yg = (Ho + s.rt - 1) / s.rt, s.n_tiles = Do * s.n_yg * s.n_xb;
+    s.grid = grid_of_tiles(s.n_tiles);
+    return s;
+}
+inline LaunchShape deconv_launch_shape(int Di, int Hi, int Wi) {
+    LaunchShape s;
+    s.rt = 1, s.n_xb = (Wi + 15) / 16, s.n_yg = Hi, s.n_tiles = Di * Hi * s.n_xb;
+    s.grid = grid_of_tiles(s.n_tiles);
+    return s;
+}
+
 template <int CIN, int COUT, int STRIDE, bool PRE, int K = 3, int KD = 3>
 int launch_conv(const ConvArgs &a0, int passes, hipStream_t st) {
     ConvArgs a = a0;
-    const long long rows = (long long)a.Do * a.Ho * ((a.Wo + 15) / 16);
-    // small levels: one row per wave so that the tiles still cover the chip
-    const bool small = rows < 8192;
-    // rows per wave: 4 (1 on the small levels).  (8 for the first layer - fewer strips per output row, 10 / 8 instead
-    // of 6 / 4 - does not fit two waves per SIMD: 500 - 800 spilled registers.)
-    constexpr int RTL = 4;
-    const int RT = small ? 1 : RTL;
-    a.n_xb = (a.Wo + 15) / 16, a.n_yg = (a.Ho + RT - 1) / RT, a.n_tiles = a.Do * a.n_yg * a.n_xb;
-    const int grid = a.n_tiles < 4096 ? (a.n_tiles + 3) / 4 : 1024;
+    const LaunchShape ls = conv_launch_shape(a.Do, a.Ho, a.Wo);
+    a.n_xb = ls.n_xb, a.n_yg = ls.n_yg, a.n_tiles = ls.n_tiles;
+    const int grid = ls.grid;
+    const bool small = ls.rt == 1;
+    constexpr int RTL = 4;                                   // = conv_launch_shape's rows per wave of the other levels
 #define ZEST_CONV(P, R) hipLaunchKernelGGL((conv3d_mfma_kernel<CIN, COUT, STRIDE, P, PRE, R, K, KD>), dim3(grid), dim3(256), 0, st, a)
     if (passes == 1) { if (small) ZEST_CONV(1, 1); else ZEST_CONV(1, RTL); }
     else { if (small) ZEST_CONV(3, 1); else ZEST_CONV(3, RTL); }
@@ -595,6 +616,24 @@ int launch_conv(const ConvArgs &a0, int passes, hipStream_t st) {
 }  // namespace
 
 extern "C" int zest_costreg_stat_rows(void) { return kStatRows + 1; }
+
+extern "C" int zest_costreg_conv_launch_shape(int Do, int Ho, int Wo, int *rows_per_wave, int *n_tiles, int *n_wg) {
+    ZEST_CHECK_ARG(Do >= 1 && Ho >= 1 && Wo >= 1 && (long long)Do * Ho * ((Wo + 15) / 16) < (1ll << 31),
+                   "zest_costreg_conv_launch_shape: bad shape %d x %d x %d", Do, Ho, Wo);
+    const LaunchShape s = conv_launch_shape(Do, Ho, Wo);
+    if (rows_per_wave) *rows_per_wave = s.rt;
+    if (n_tiles) *n_tiles = s.n_tiles;
+    if (n_wg) *n_wg = s.grid;
+    return 0;
+}
+extern "C" int zest_costreg_deconv_launch_shape(int Di, int Hi, int Wi, int *n_tiles, int *n_wg) {
+    ZEST_CHECK_ARG(Di >= 1 && Hi >= 1 && Wi >= 1 && (long long)Di * Hi * ((Wi + 15) / 16) < (1ll << 31),
+                   "zest_costreg_deconv_launch_shape: bad shape %d x %d x %d", Di, Hi, Wi);
+    const LaunchShape s = deconv_launch_shape(Di, Hi, Wi);
+    if (n_tiles) *n_tiles = s.n_tiles;
+    if (n_wg) *n_wg = s.grid;
+    return 0;
+}
 
 static size_t conv_packed_bytes(int cin, int cout, int passes, int k, int kd) {
     const int opt = cin / 8, cpr = (k * opt + 3) / 4, nt = (cout + 15) / 16;
@@ -676,9 +715,9 @@ extern "C" int zest_costreg_deconv_fwd(const float *in0, const float *pre0, cons
                    "zest_costreg_deconv_fwd: pointers must be 16-byte aligned");
     ZEST_CHECK_ARG(passes == 1 || passes == 3, "zest_costreg_deconv_fwd: passes %d", passes);
     ZEST_CHECK_ARG(Di >= 1 && Hi >= 1 && Wi >= 1 && (long long)Di * Hi * Wi * 8 * cout < (1ll << 31), "zest_costreg_deconv_fwd: bad shape");
-    DeconvArgs a{in0, pre0, in1, pre1, (const uint4 *)w_packed, out, stats, Di, Hi, Wi, 0, 0};
-    a.n_xb = (Wi + 15) / 16, a.n_tiles = Di * Hi * a.n_xb;
-    const dim3 grid(a.n_tiles < 4096 ? (a.n_tiles + 3) / 4 : 1024), block(256);
+    const LaunchShape ls = deconv_launch_shape(Di, Hi, Wi);
+    DeconvArgs a{in0, pre0, in1, pre1, (const uint4 *)w_packed, out, stats, Di, Hi, Wi, ls.n_xb, ls.n_tiles};
+    const dim3 grid(ls.grid), block(256);
     const hipStream_t st = (hipStream_t)stream;
     const int key = cin * 100 + cout;
 #define ZEST_DECONV_P(CI, CO, TWO)                                                                           \

@@ -84,6 +84,8 @@ _SIGS = {
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "zest_costreg_stat_rows": (_i, []),
+    "zest_costreg_conv_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "zest_costreg_deconv_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "zest_conv2d_packed_bytes": (_sz, [_i, _i, _i, _i]),
     "zest_conv2d_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_costreg_packed_bytes": (_sz, [_i, _i, _i]),
@@ -364,6 +366,23 @@ def volume_cost_cl(feats, imgs_lr, proj, depth, pad=0, feats_cl=None):
 
 def costreg_stat_rows():
     return int(lib().zest_costreg_stat_rows())
+
+
+def costreg_conv_launch_shape(Do, Ho, Wo):
+    """-> (rows per wave, tiles, workgroups) of the convolution kernel for an OUTPUT of Do x Ho x Wo voxels (a batch of
+    N images: Do = N).  Host arithmetic, the same code the launch runs."""
+    rt, tiles, wgs = _i(0), _i(0), _i(0)
+    _check(lib().zest_costreg_conv_launch_shape(int(Do), int(Ho), int(Wo), C.byref(rt), C.byref(tiles), C.byref(wgs)),
+           "zest_costreg_conv_launch_shape")
+    return rt.value, tiles.value, wgs.value
+
+
+def costreg_deconv_launch_shape(Di, Hi, Wi):
+    """-> (tiles, workgroups) of the transposed-convolution kernel for an INPUT of Di x Hi x Wi voxels."""
+    tiles, wgs = _i(0), _i(0)
+    _check(lib().zest_costreg_deconv_launch_shape(int(Di), int(Hi), int(Wi), C.byref(tiles), C.byref(wgs)),
+           "zest_costreg_deconv_launch_shape")
+    return tiles.value, wgs.value
 
 
 def costreg_stats(cout, device):

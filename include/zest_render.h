@@ -379,7 +379,19 @@ int zest_mlp_train16_bwd(const zest_mlp_desc *desc, const void *packed_bwd, cons
 /* ---- MLP ---------------------------------------------------------------------------
  * Weights are re-packed once per parameter update into the order the MFMA engine
  * streams them.  zest_mlp_packed_bytes gives the buffer size; params is an array of
- * 2*ZEST_P_COUNT device pointers (weight, bias per ZEST_P_* slot, NULL where absent). */
+ * 2*ZEST_P_COUNT device pointers (weight, bias per ZEST_P_* slot, NULL where absent).
+ * Layout of `packed`, opaque to the caller and all of it inside zest_mlp_packed_bytes:
+ *   ZEST_PREC_F32: one stream (bias area, then tiles), the network op for op.
+ *   ZEST_PREC_BF16 / _F16 / _F16X3, three regions, each a whole number of KiB:
+ *     1. the plain stream at offset 0: every Linear of the network as its own layer.  This is what
+ *        zest_mlp_train16_fwd reads (its backward needs the feature_linear output);
+ *     2. a scratch of 129 KiB: Wc = Wvh Wf [128][256] and bc = Wvh bf + bv [128] in fp32, where Wf, bf are
+ *        feature_linear and Wvh the first 256 columns of views_linears.0 (bias bv).  zest_mlp_pack computes
+ *        them on the device, accumulating in float64 in a fixed order: equal weights give equal bytes;
+ *     3. the inference stream: the same network without the feature_linear layer, its view layer being
+ *        relu(Wc h + Wvd PE(dir) + bc) - the same map, since the reference applies no activation between
+ *        the two Linears.  zest_mlp_fwd and zest_render_fused_fwd read this one.
+ * No process state belongs to a packed buffer; it is valid until the parameters change. */
 size_t zest_mlp_packed_bytes(const zest_mlp_desc *desc, int precision);
 int    zest_mlp_pack(const zest_mlp_desc *desc, int precision, const float *const *params,
                      void *packed, void *stream);

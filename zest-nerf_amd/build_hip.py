@@ -39,7 +39,7 @@ VARIANTS = [("fused_%s_%s" % (pt, tag),
              # kernels (at 256 VGPRs) answer with a few more spills and keep the default
              (["-mllvm", "-amdgpu-use-amdgpu-trackers=1"] if ((nts or ntd) and pt != "x3") else []) +
              # the featureless single-net kernel (the headline): LLVM's max-ILP scheduling strategy, +1.3 % in three A/B
-             # pairs in bf16 (226 instead of 246 VGPRs, no scratch), +1.7 % in split fp16 (profiles/r03_ab_sched.txt); the
+             # pairs in bf16 (226 instead of 246 VGPRs then; 190 with the folded view layer; no scratch), +1.7 % in split fp16 (profiles/r03_ab_sched.txt); the
              # feature kernels lose 1 % (bf16) or gain nothing (split fp16) with it, the post-RA scheduler switched off
              # loses 1 - 3 %
              (["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if tag == "s0" else []))

@@ -386,7 +386,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
     constexpr bool MOD_S = NT_FEAT_S > 0, MOD_D = NT_FEAT_D > 0;
     constexpr int NP = ep_parts(EP), CB = fused_cb(EP), BS = 16 * CB;
     if constexpr (EP == ZEST_PREC_F16) engine_fp16_overflow_clamp();
-    constexpr int UNITS_S = stream_units(4, NT_FEAT_S, NP), UNITS_D = DYN ? stream_units(6, NT_FEAT_D, NP) : 0;
+    // both nets are read from their inference streams (mlp_plan.h: feature_linear folded into the view layer)
+    constexpr int UNITS_S = stream_units(4, NT_FEAT_S, NP, true), UNITS_D = DYN ? stream_units(6, NT_FEAT_D, NP, true) : 0;
     using Ring = RingTiles<kFusedWaves, UNITS_S, UNITS_D>;
     // LDS: weight ring | cameras of both nets | per-lane (z, dist) of the pass's samples | ring flags |
     // block records | sample coordinates (the point operand is rebuilt from them at the skip layer) |
@@ -589,7 +590,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
         };
         ZEST_STAMP(st_enc);
         if constexpr (ZEST_REBUILD_PTS) {
-            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true>(tiles, unit, pts_static, feat_s,
+            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true, true>(tiles, unit, pts_static, feat_s,
                                                         views_of(a.st, cams_s), head_s, rgb_s);
         } else {
             OpArr<2, NP> pts_keep[CB];
@@ -598,7 +599,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
             };
-            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true>(tiles, unit, pts_copy, feat_s,
+            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true, true>(tiles, unit, pts_copy, feat_s,
                                                         views_of(a.st, cams_s), head_s, rgb_s);
         }
         ZEST_STAMP(st_eng);
@@ -655,7 +656,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
             }
             ZEST_STAMP(st_comp);
             if constexpr (ZEST_REBUILD_PTS) {
-                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true>(tiles, unit, pts_dynamic, feat_d,
+                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true, true>(tiles, unit, pts_dynamic, feat_d,
                                                             views_of(a.dy, cams_d), head_d, rgb_d);
             } else {
                 OpArr<3, NP> pts_keep[CB];
@@ -664,7 +665,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
 #pragma unroll
                     for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
                 };
-                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true>(tiles, unit, pts_copy, feat_d,
+                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true, true>(tiles, unit, pts_copy, feat_d,
                                                             views_of(a.dy, cams_d), head_d, rgb_d);
             }
             ZEST_STAMP(st_eng);
@@ -749,7 +750,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
         ZEST_RETURN_LAUNCH("zest_render_fused_fwd(" #ptag "_" #tag ")");                         \
     }                                                                                            \
     int fused_units_##ptag##_##tag(int which) {                                                  \
-        return which == 0 ? stream_units(4, NTS, ep_parts(EP)) : (DYN ? stream_units(6, NTD, ep_parts(EP)) : 0); \
+        return which == 0 ? stream_units(4, NTS, ep_parts(EP), true) : (DYN ? stream_units(6, NTD, ep_parts(EP), true) : 0); \
     }
 
 #define ZEST_FUSED_DECL1(ptag, tag)                                                     \

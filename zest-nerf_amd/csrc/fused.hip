@@ -27,9 +27,10 @@ bool fill_net(const zest_mlp_desc *d, const void *packed, const zest_view_set *v
     if (d->in_ch_pts != pts_ch) return *err = "unexpected in_ch_pts for this slot", false;
     if (d->net_type != 0 && d->net_type != 2) return *err = "net_type must be 0 ('v0') or 2 ('v2')", false;
     zest::MlpPlan plan;
-    if (!zest::build_plan(*d, precision, zest::ORDER_ACC, &plan, err, false)) return false;
-    n->bias = (const float *)packed;
-    n->tiles = (const uint4 *)((const char *)packed + plan.bias_bytes);
+    // the inference stream of the packed buffer (mlp_plan.h: behind the plain stream and the fold's scratch)
+    if (!zest::build_plan(*d, precision, zest::ORDER_ACC, &plan, err, false, true)) return false;
+    n->bias = (const float *)((const char *)packed + plan.stream_off);
+    n->tiles = (const uint4 *)((const char *)n->bias + plan.bias_bytes);
     n->head = d->head, n->v2 = d->net_type == 2;
     *nt_feat = d->use_feat ? plan.nt_feat : 0;
     *units = plan.n_tiles;

@@ -27,6 +27,7 @@ std::mutex g_mu;
 std::map<std::tuple<int, int, int, int, int, int, int, int, int, int, int, int>, DevPlan *> g_plans;   // per shape AND device
 
 constexpr int kOrderBwd = 99;       // key of the training path's backward-data stream (bf16, build_bwd_plan)
+constexpr int kOrderFold = 98;      // key of the engine's inference stream (ORDER_ACC, feature_linear folded: mlp_plan.h)
 
 // Plans are built once per (shape, precision, order, device) and kept for the life of the process: a plan's gather
 // tables live in the memory of the device that was current when they were uploaded, so the current device is
@@ -42,8 +43,9 @@ DevPlan *get_plan(const zest_mlp_desc &d, int precision, int order, bool need_ta
     if (!dp) {
         dp = new DevPlan();
         const char *err = nullptr;
-        const bool ok = order == kOrderBwd ? zest::build_bwd_plan(d, &dp->plan, &err)
-                                           : zest::build_plan(d, precision, order, &dp->plan, &err);
+        const bool ok = order == kOrderBwd    ? zest::build_bwd_plan(d, &dp->plan, &err)
+                        : order == kOrderFold ? zest::build_plan(d, precision, zest::ORDER_ACC, &dp->plan, &err, true, true)
+                                              : zest::build_plan(d, precision, order, &dp->plan, &err);
         if (!ok) {
             zest_set_error("MLP shape not supported: %s", err);
             delete dp;
@@ -76,8 +78,31 @@ inline int order_for(int precision) {
 }
 
 struct ParamTable {
-    const float *p[2 * ZEST_P_COUNT];
+    const float *p[2 * zest::kParamSlots];     // the caller's parameters, then the fold scratch (kFoldSlot: Wc, bc)
 };
+
+// Folded view layer (mlp_plan.h): Wc = Wvh Wf [W/2][W] and bc = Wvh bf + bv [W/2], with Wvh the first W columns of
+// views_linears.0 (leading dimension ld_v).  One thread per output walks k = 0 .. W-1 in order with a float64
+// accumulator - every product of two fp32 values is exact in it - and rounds once to fp32: the same weights give
+// the same bits on every pack.  Blocks 0 .. W/2-1: one row of Wc each; block W/2: bc and the zero padding behind it.
+__global__ __launch_bounds__(zest::kW) void fold_view_kernel(const float *__restrict__ wv, const float *__restrict__ bv,
+                                                             const float *__restrict__ wf, const float *__restrict__ bf,
+                                                             int ld_v, float *__restrict__ wc, float *__restrict__ bc) {
+    constexpr int W = zest::kW;
+    const int r = blockIdx.x, c = threadIdx.x;
+    if (r < W / 2) {
+        double acc = 0.0;
+        for (int k = 0; k < W; k++) acc += (double)wv[(size_t)r * ld_v + k] * (double)wf[(size_t)k * W + c];
+        wc[(size_t)r * W + c] = (float)acc;
+    } else if (c < W / 2) {
+        double acc = 0.0;
+        for (int k = 0; k < W; k++) acc += (double)wv[(size_t)c * ld_v + k] * (double)bf[k];
+        bc[c] = (float)(acc + (double)bv[c]);
+    } else {
+        bc[c] = 0.0f;       // the scratch's padding: every byte of a packed buffer is written
+    }
+}
+static_assert(zest::kFoldScratchBytes == zest::kFoldBiasOffset + (size_t)zest::kW * 4, "bc [W/2] and W/2 floats of padding");
 
 // PREC: element type of the packed tiles.  ZEST_PREC_F16X3: a unit flagged 1 in unit_part holds
 // the scaled remainders fp16((w - fp16(w)) * 2^11) of the unit in front of it.
@@ -262,7 +287,7 @@ int pack_bwd_stream(const zest_mlp_desc &d, const float *const *params, void *pa
     DevPlan *dp = get_plan(d, ZEST_PREC_BF16, kOrderBwd, true);
     if (!dp) return (int)hipErrorInvalidValue;
     const MlpPlan &p = dp->plan;
-    ParamTable pt;
+    ParamTable pt = {};
     for (int i = 0; i < 2 * ZEST_P_COUNT; i++) pt.p[i] = params[i];
     const size_t n_w = p.tile_src.size(), n_h = p.hdr_src.size();
     hipLaunchKernelGGL(pack_kernel<ZEST_PREC_BF16>, dim3(zest_div_up(n_w, 256)), dim3(256), 0, stream, pt, dp->tile_src,
@@ -275,6 +300,10 @@ int pack_bwd_stream(const zest_mlp_desc &d, const float *const *params, void *pa
 
 extern "C" size_t zest_mlp_packed_bytes(const zest_mlp_desc *desc, int precision) {
     if (!desc) return 0;
+    if (zest::prec_is_engine(precision)) {      // plain stream | fold scratch | inference stream (mlp_plan.h)
+        DevPlan *df = get_plan(*desc, precision, kOrderFold, false);
+        return df ? df->plan.stream_off + df->plan.bytes : 0;
+    }
     DevPlan *dp = get_plan(*desc, precision, order_for(precision), false);
     return dp ? dp->plan.bytes : 0;
 }
@@ -285,7 +314,9 @@ extern "C" int zest_mlp_pack(const zest_mlp_desc *desc, int precision, const flo
     DevPlan *dp = get_plan(*desc, precision, order_for(precision), true);
     if (!dp) return (int)hipErrorInvalidValue;
     const MlpPlan &p = dp->plan;
-    ParamTable pt;
+    DevPlan *df = zest::prec_is_engine(precision) ? get_plan(*desc, precision, kOrderFold, true) : nullptr;
+    if (zest::prec_is_engine(precision) && !df) return (int)hipErrorInvalidValue;
+    ParamTable pt = {};
     for (int i = 0; i < 2 * ZEST_P_COUNT; i++) pt.p[i] = params[i];
     // every parameter the gather tables reference must be present
     bool need[ZEST_P_COUNT] = {};
@@ -298,24 +329,39 @@ extern "C" int zest_mlp_pack(const zest_mlp_desc *desc, int precision, const flo
         ZEST_CHECK_ARG(!need[i] || (params[2 * i] && params[2 * i + 1]),
                        "zest_mlp_pack: parameter slot %d (weight and bias) is required", i);
     ZEST_CHECK_ARG(((uintptr_t)packed & 15) == 0, "zest_mlp_pack: packed must be 16-byte aligned");
-    const size_t n_w = p.tile_src.size(), n_b = p.bias_src.size();
-    const size_t n = n_w > n_b ? n_w : n_b;
-    void *w_out = (char *)packed + p.bias_bytes;
+    // one stream of the buffer: the gather through plan q's tables, written at `base`
+    auto pack_stream = [&](const DevPlan *q, char *base) {
+        const size_t n_w = q->plan.tile_src.size(), n_b = q->plan.bias_src.size();
+        const size_t n = n_w > n_b ? n_w : n_b;
+        void *w_out = base + q->plan.bias_bytes;
 #define ZEST_PACK(PREC)                                                                            \
     hipLaunchKernelGGL(pack_kernel<PREC>, dim3(zest_div_up(n, 256)), dim3(256), 0, (hipStream_t)stream, \
-                       pt, dp->tile_src, n_w, dp->bias_src, n_b, dp->unit_part, (float *)packed, w_out)
-    if (zest::prec_is_engine(precision)) {
-        if (precision == ZEST_PREC_BF16) ZEST_PACK(ZEST_PREC_BF16);
-        else if (precision == ZEST_PREC_F16) ZEST_PACK(ZEST_PREC_F16);
-        else ZEST_PACK(ZEST_PREC_F16X3);
-        const size_t n_h = p.hdr_src.size();
-        if (n_h)     // same stream, after the tile pass that zero-filled the header units
-            hipLaunchKernelGGL(pack_headers_kernel, dim3(zest_div_up(n_h, 256)), dim3(256), 0,
-                               (hipStream_t)stream, pt, dp->hdr_src, n_h, (char *)w_out);
-    } else {
-        ZEST_PACK(ZEST_PREC_F32);
-    }
+                       pt, q->tile_src, n_w, q->bias_src, n_b, q->unit_part, (float *)base, w_out)
+        if (zest::prec_is_engine(precision)) {
+            if (precision == ZEST_PREC_BF16) ZEST_PACK(ZEST_PREC_BF16);
+            else if (precision == ZEST_PREC_F16) ZEST_PACK(ZEST_PREC_F16);
+            else ZEST_PACK(ZEST_PREC_F16X3);
+            const size_t n_h = q->plan.hdr_src.size();
+            if (n_h)     // same stream, after the tile pass that zero-filled the header units
+                hipLaunchKernelGGL(pack_headers_kernel, dim3(zest_div_up(n_h, 256)), dim3(256), 0,
+                                   (hipStream_t)stream, pt, q->hdr_src, n_h, (char *)w_out);
+        } else {
+            ZEST_PACK(ZEST_PREC_F32);
+        }
 #undef ZEST_PACK
+    };
+    pack_stream(dp, (char *)packed);            // the plain stream at offset 0 (training forward, fp32 kernel)
+    if (df) {
+        // the product of feature_linear and the view layer into the scratch, then the inference stream, whose
+        // tables gather from it as slot kFoldSlot (same hip stream: in order)
+        float *wc = (float *)((char *)packed + zest::fold_scratch_offset(p.bytes));
+        float *bc = (float *)((char *)wc + zest::kFoldBiasOffset);
+        hipLaunchKernelGGL(fold_view_kernel, dim3(zest::kW / 2 + 1), dim3(zest::kW), 0, (hipStream_t)stream,
+                           params[2 * ZEST_P_VIEWS], params[2 * ZEST_P_VIEWS + 1], params[2 * ZEST_P_FEATURE],
+                           params[2 * ZEST_P_FEATURE + 1], zest::kW + desc->in_ch_views, wc, bc);
+        pt.p[2 * zest::kFoldSlot] = wc, pt.p[2 * zest::kFoldSlot + 1] = bc;
+        pack_stream(df, (char *)packed + df->plan.stream_off);
+    }
     ZEST_RETURN_LAUNCH("zest_mlp_pack");
 }
 
@@ -324,12 +370,13 @@ extern "C" int zest_mlp_fwd(const zest_mlp_desc *desc, int precision, const void
     if (M == 0) return 0;                       // an empty batch is a no-op (its tensors have no storage)
     ZEST_CHECK_ARG(desc && packed && x && out, "zest_mlp_fwd: null argument");
     ZEST_CHECK_ARG(M >= 0, "zest_mlp_fwd: M=%d", M);
-    DevPlan *dp = get_plan(*desc, precision, order_for(precision), false);
+    // the engine reads the inference stream of the buffer, the fp32 kernel its only one (stream_off = 0)
+    DevPlan *dp = get_plan(*desc, precision, zest::prec_is_engine(precision) ? kOrderFold : order_for(precision), false);
     if (!dp) return (int)hipErrorInvalidValue;
     if (M == 0) return 0;
     const MlpPlan &p = dp->plan;
-    const float *bias = (const float *)packed;
-    const void *tiles = (const char *)packed + p.bias_bytes;
+    const float *bias = (const float *)((const char *)packed + p.stream_off);
+    const void *tiles = (const char *)bias + p.bias_bytes;
     if (precision == ZEST_PREC_F32) {
         const F32Prog pr = make_f32_prog(p);
         const size_t lds = (size_t)(pr.rows_pts + pr.rows_feat + 32 + 2 * pr.W) * 32 * sizeof(float);

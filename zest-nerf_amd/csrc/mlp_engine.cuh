@@ -37,15 +37,18 @@ typedef __attribute__((address_space(3))) int lds_int;                // an int 
 namespace zest {
 
 // units in the stream of one net (mirror of build_plan for ORDER_ACC, checked on the host)
-// (parts: stream units per weight tile, 2 for the split fp16 pair)
-constexpr int stream_units_raw(int nt_pts, int nt_feat, int parts = 1) {
+// (parts: stream units per weight tile, 2 for the split fp16 pair; fold: the inference stream, whose view layer
+// carries feature_linear - mlp_plan.h - so the 8 row blocks of op D+1 are absent)
+constexpr int stream_units_raw(int nt_pts, int nt_feat, int parts = 1, bool fold = false) {
     const int mod = nt_feat * parts, P = nt_pts * parts, H = 16 * parts;   // mod: modulation units per row block (0 = off)
     return 8 * (1 + mod + P) + 6 * 8 * (1 + mod + H) + 8 * (1 + mod + P + H)   // trunk
-           + (1 + H) + 8 * (1 + H) + 4 * (1 + H + 2 * parts) + (1 + H / 2);     // heads
+           + (1 + H) + (fold ? 0 : 8 * (1 + H)) + 4 * (1 + H + 2 * parts) + (1 + H / 2);     // heads
 }
-constexpr int stream_units(int nt_pts, int nt_feat, int parts = 1) {
-    return (stream_units_raw(nt_pts, nt_feat, parts) + kStreamAlign - 1) / kStreamAlign * kStreamAlign;
+constexpr int stream_units(int nt_pts, int nt_feat, int parts = 1, bool fold = false) {
+    return (stream_units_raw(nt_pts, nt_feat, parts, fold) + kStreamAlign - 1) / kStreamAlign * kStreamAlign;
 }
+static_assert(stream_units_raw(4, 0) == 1262 && stream_units_raw(4, 0, 1, true) == 1126 &&
+              stream_units(4, 0, 1, true) == 9 * kStreamAlign, "unit counts of the headline net (DESIGN.md 3.1)");
 
 // ---- weight source: LDS ring fed by LDS-DMA -----------------------------------------------
 // The ring holds kRingUnits KiB = kSlots chunks of kChunk units.  All NW waves of the
@@ -668,8 +671,11 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
 // out copies);
 // `views_fn(views)` builds the direction operand when it is first needed (op 10).  Results per column block: head (lane group g: rows 4g .. 4g+3 of the head
 // tile; row 0 alpha, rows 1.. extra heads) and rgb (group 0: rows 0-2), raw.
-template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool MCACHE = false, class Tiles, class PtsFn, class ViewsFn,
-          class Sink = NoSink>
+// FOLD: the stream is the inference stream (mlp_plan.h): no feature_linear layer (sink id 8 is never seen), the
+// view layer multiplies the trunk output itself.  The training forward, whose backward needs the feature_linear
+// output in the stash, runs FOLD = false on the plain stream.
+template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool MCACHE = false, bool FOLD = false, class Tiles,
+          class PtsFn, class ViewsFn, class Sink = NoSink>
 __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, PtsFn pts_fn,
                                                const OpArr<NU_FEAT / 2, ep_parts(EP)> (&feat)[CB], ViewsFn views_fn,
                                                f32x4 (&head)[CB], f32x4 (&rgb)[CB], const Sink &sink = Sink()) {
@@ -700,21 +706,24 @@ __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, Pt
     engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hA, none, feat, hB, unused, 7, sink);
     // trunk output in hB
     engine_layer<EP, CB, 1, 8, 0, false, KF, false, 1, V2, 0>(tiles, unit, hB, none, feat, hA, head);
-    engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2, 0>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
+    if constexpr (!FOLD)
+        engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2, 0>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
+    // view layer: on the feature_linear output (hA -> hB), or folded on the trunk output itself (hB -> hA)
+    OpArr<8, NP> (&vin)[CB] = FOLD ? hB : hA, (&vout)[CB] = FOLD ? hA : hB;
     OpArr<1, NP> views[CB];
     views_fn(views);
-    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2, 0>(tiles, unit, hA, views, feat, hB, unused, 9, sink);
-    // rgb: 128 hidden features = first 4 k-tiles of hB
+    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2, 0>(tiles, unit, vin, views, feat, vout, unused, 9, sink);
+    // rgb: 128 hidden features = first 4 k-tiles of the view layer's output
     OpArr<4, NP> h128[CB];
 #pragma unroll
     for (int cb = 0; cb < CB; cb++)
 #pragma unroll
         for (int pt = 0; pt < NP; pt++)
 #pragma unroll
-            for (int k = 0; k < 4; k++) h128[cb].t[pt][k] = hB[cb].t[pt][k];
-    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2, 0>(tiles, unit, h128, none, feat, hA, rgb);
-    tiles.finish(unit, unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP));
-    unit = unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP);
+            for (int k = 0; k < 4; k++) h128[cb].t[pt][k] = vout[cb].t[pt][k];
+    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2, 0>(tiles, unit, h128, none, feat, vin, rgb);
+    tiles.finish(unit, unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD));
+    unit = unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD);
 }
 
 // standalone launcher (mlp.hip -> zest_mlp_fwd)

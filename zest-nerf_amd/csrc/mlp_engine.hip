@@ -59,7 +59,9 @@ template <int EP, int NT_PTS, bool MOD, int NT_FEAT, bool TRAIN = false, bool V2
 __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kernel(
     const uint4 *__restrict__ tiles_g, const float *__restrict__ x, int M, int P, int F, int C_in, int C_out, int head,
     int act_out, float *__restrict__ out, uint4 *__restrict__ stash_tiles = nullptr, uint2 *__restrict__ stash_masks = nullptr) {
-    constexpr int NP = ep_parts(EP), CB = mlp_cb(EP), UNITS = stream_units(NT_PTS, MOD ? NT_FEAT : 0, NP);
+    // inference reads the folded stream (mlp_plan.h); the training forward stashes the feature_linear output
+    constexpr bool FOLD = !TRAIN;
+    constexpr int NP = ep_parts(EP), CB = mlp_cb(EP), UNITS = stream_units(NT_PTS, MOD ? NT_FEAT : 0, NP, FOLD);
     using Ring = RingTiles<kMlpWaves, UNITS, 0>;
     if constexpr (EP == ZEST_PREC_F16) engine_fp16_overflow_clamp();
     __shared__ __attribute__((aligned(16))) char lds[kRingUnits * 1024 + 2 * kSlots * 4];
@@ -129,9 +131,9 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
         };
         if constexpr (TRAIN) {
             const StashSink<CB> sink{stash_tiles, stash_masks, (long long)pass * kMlpWaves + wave, lane, {}, {}};
-            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt, sink);
+            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, false, false>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt, sink);
         } else {
-            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt);
+            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, false, true>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt);
         }
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
@@ -162,9 +164,10 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
 template <int EP, int NT_PTS, bool MOD, int NT_FEAT, bool TRAIN = false, bool V2 = false>
 static int launch_one(const MlpPlan &p, const void *tiles, const float *x, int M,
                       float *out, hipStream_t stream, void *stash_tiles = nullptr, void *stash_masks = nullptr) {
-    constexpr int units = stream_units(NT_PTS, MOD ? NT_FEAT : 0, ep_parts(EP));
-    if (p.n_tiles != units) {
-        zest_set_error("zest_mlp_fwd(engine): plan has %d stream units, kernel expects %d", p.n_tiles, units);
+    constexpr int units = stream_units(NT_PTS, MOD ? NT_FEAT : 0, ep_parts(EP), !TRAIN);
+    if (p.n_tiles != units || (p.fold != 0) != !TRAIN) {
+        zest_set_error("zest_mlp_fwd(engine): plan has %d stream units (fold %d), kernel expects %d (fold %d)", p.n_tiles,
+                       p.fold, units, TRAIN ? 0 : 1);
         return (int)hipErrorInvalidValue;
     }
     const zest_mlp_desc &d = p.desc;

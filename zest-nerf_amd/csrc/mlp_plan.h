@@ -4,7 +4,7 @@
 // each a Linear producing NJB row-blocks of 32 output features:
 //   0..D-1  trunk layers  h = relu((W h + b) (*|+) m),  m = pts_bias(feats) recomputed per tile
 //   D       head tile     rows: alpha, then w | sf(6) prob(2)      (on the trunk output)
-//   D+1     feature_linear (no activation)
+//   D+1     feature_linear (no activation)              (absent from the inference stream, below)
 //   D+2     views_linears.0 on [feature | PE(dir)], relu
 //   D+3     rgb_linear
 // The ORDER_ACC engine and everything below "bf16 training path" are written for D = 8, W = 256,
@@ -42,6 +42,19 @@
 // units, hi = fp16(w) and lo = fp16((w - hi) * 2^11) (MlpPlan::parts = 2; the tile counts nt_*
 // stay logical, unit counts double), and the kernel forms a product as
 // hi*hi + 2^-11 (hi*lo + lo*hi).
+//
+// Inference stream (ORDER_ACC, build_plan's `fold`).  Nothing stands between feature_linear and the view
+// layer (networks.py:198-204), so for a forward that needs no feature_linear output the two are one map of
+// the trunk output: with Wv = [Wvh | Wvd],
+//   relu(Wv [Wf h + bf | PE(dir)] + bv) = relu((Wvh Wf) h + Wvd PE(dir) + (Wvh bf + bv)).
+// The folded plan has no op D+1 (njb = 0) and its op D+2 reads [h (8 k-tiles) | views (1 k-tile)] with
+// weights Wc = Wvh Wf and bias bc = Wvh bf + bv, which the packer computes once per pack into a scratch
+// region of the packed buffer (kFoldSlot: one more parameter slot of the gather tables).  136 units
+// and 256 MFMAs per 32 samples fewer.  A packed buffer of an engine precision holds both streams:
+//   [plain stream | fold scratch (kFoldScratchBytes) | inference stream]      (fold_scratch_offset,
+// infer_stream_offset below).  The plain stream feeds the bf16 training forward, whose backward needs the
+// feature_linear output; the fused renderer and zest_mlp_fwd read the inference stream.  The exact-product
+// fp32 plan (ORDER_NATURAL) is never folded: it stays the op-for-op parity mode.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -80,6 +93,18 @@ constexpr int kW = 256;            // default trunk width (every shipped config:
 constexpr int kNumOps = 12;        // op slots: depth <= 8
 constexpr int kMaxSeg = 2;
 constexpr int kStreamAlign = 128;  // units (KiB): ring size the bf16 stream is padded to
+
+// ---- folded view layer (inference stream) ----------------------------------------------------
+// Scratch of the fold: Wc [kW/2][kW] fp32, then bc [kW/2] fp32, padded to whole KiB.  The gather tables of a
+// folded plan address it as parameter slot kFoldSlot (weight = Wc, bias = bc).
+constexpr int kFoldSlot = ZEST_P_COUNT;
+constexpr int kParamSlots = ZEST_P_COUNT + 1;                      // slots a gather source may name
+constexpr size_t kFoldBiasOffset = (size_t)(kW / 2) * kW * 4;      // bytes from the scratch start to bc
+constexpr size_t kFoldScratchBytes = (kFoldBiasOffset + (size_t)(kW / 2) * 4 + 1023) / 1024 * 1024;
+// layout of an engine-precision packed buffer, from the size of its plain stream (MlpPlan::bytes of the
+// unfolded plan): the one definition for the packer and every consumer
+constexpr size_t fold_scratch_offset(size_t plain_bytes) { return plain_bytes; }
+constexpr size_t infer_stream_offset(size_t plain_bytes) { return plain_bytes + kFoldScratchBytes; }
 
 // slot-order conventions for operands that are produced from accumulator tiles
 enum SlotOrder {
@@ -125,6 +150,8 @@ struct MlpPlan {
     int tail_unit0;                // backward stream: first unit of the modulation^T tail (after the padded ring part)
     int headers;                   // 1: ORDER_ACC stream with inline header units
     int parts;                     // stream units per weight tile: 1, or 2 (hi, lo) for ZEST_PREC_F16X3
+    int fold;                      // 1: inference stream (feature_linear folded into the view layer, no op D+1)
+    size_t stream_off;             // fold: byte offset of this stream in the packed buffer (infer_stream_offset); else 0
     int n_tiles, n_bias_blocks;    // n_tiles includes headers and tail padding
     size_t bias_bytes, bytes;      // bias area (padded to 1 KiB) and total
     OpPlan op[kNumOps];
@@ -189,7 +216,8 @@ int build_dw_jobs(const zest_mlp_desc &d, std::vector<DwJob> *jobs, const char *
 
 // Builds the plan; returns false (with *err set) for shapes the kernels do not cover.
 // with_tables = false skips the packer's gather tables (cheap: launch-time shape queries).
+// fold (ORDER_ACC only): the inference stream, see the header comment.
 bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *out, const char **err,
-                bool with_tables = true);
+                bool with_tables = true, bool fold = false);
 
 }  // namespace zest

@@ -67,7 +67,7 @@ struct RowSrc { int param, row; };       // param < 0: zero row
 }  // namespace
 
 bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, const char **err,
-                bool with_tables) {
+                bool with_tables, bool fold) {
     static const char *e_prec = "precision must be ZEST_PREC_F32, _BF16, _F16 or _F16X3";
     static const char *e_pts = "in_ch_pts must be 63 (xyz, L=10) or 84 (xyzt, L=10)";
     static const char *e_views = "in_ch_views must be 27 (L=4)";
@@ -76,6 +76,7 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
     if (precision != ZEST_PREC_F32 && !prec_is_engine(precision)) return *err = e_prec, false;
     if ((order == ORDER_ACC) != prec_is_engine(precision))
         return *err = "ORDER_ACC goes with the engine precisions, ORDER_NATURAL with fp32", false;
+    if (fold && order != ORDER_ACC) return *err = "only the engine's stream (ORDER_ACC) has a folded form", false;
     if (d.in_ch_pts != 63 && d.in_ch_pts != 84) return *err = e_pts, false;
     if (d.in_ch_views != 27) return *err = e_views, false;
     const int F = d.use_feat ? d.in_ch_feat : 0;
@@ -96,6 +97,7 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
     p.n_ops = D + 4;
     p.spt = prec_is_engine(precision) ? 8 : 4;
     p.parts = precision == ZEST_PREC_F16X3 ? 2 : 1;
+    p.fold = fold ? 1 : 0, p.stream_off = 0;
     const int spt = p.spt, C = d.in_ch_pts == 63 ? 3 : 4, V = d.use_feat ? (F - 8) / 4 : 0;
     if (order == ORDER_ACC) {
         // "slots" are positions here and a tile (16 rows x 32 positions) covers half a k-tile's
@@ -131,6 +133,7 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
         if (o > 0 && o < D && (sh.skip_mask >> (o - 1) & 1))
             op.nseg = 2, op.seg[0] = {SEG_PTS, p.nt_pts}, op.seg[1] = {SEG_H, p.nt_h};
         if (o == D) op.njb = 1;
+        if (o == D + 1 && fold) op.njb = 0;            // folded into the view layer: no units, no bias block
         if (o == D + 2) op.njb = Wd / 64, op.relu = 1, op.nseg = 2, op.seg[1] = {SEG_VIEWS, p.nt_views};
         if (o == D + 3) op.njb = 1, op.seg[0] = {SEG_H, p.nt_h128};
         op.tiles_per_jb = (op.mod ? p.nt_feat : 0) * p.parts + p.headers;
@@ -142,6 +145,11 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
     p.n_tiles = tile, p.n_bias_blocks = bblk;
     p.bias_bytes = (size_t)round_up(bblk * 128, 1024);
     p.bytes = p.bias_bytes + (size_t)tile * 1024;
+    if (fold) {                 // the stream sits behind the plain one and the fold's scratch
+        MlpPlan plain;
+        if (!build_plan(d, precision, order, &plain, err, false, false)) return false;
+        p.stream_off = infer_stream_offset(plain.bytes);
+    }
 
     if (!with_tables) return true;
     // ---- gather tables -------------------------------------------------------------------
@@ -156,7 +164,7 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
     auto row_src = [&](int o, int row) -> RowSrc {
         if (o < D) return {ZEST_P_PTS0 + o, row};
         if (o == D + 1) return {ZEST_P_FEATURE, row};
-        if (o == D + 2) return {row < Wd / 2 ? ZEST_P_VIEWS : -1, row};
+        if (o == D + 2) return {row < Wd / 2 ? (fold ? kFoldSlot : ZEST_P_VIEWS) : -1, row};
         if (o == D + 3) return {row < 3 ? ZEST_P_RGB : -1, row};
         // head tile: row 0 alpha, then the extra heads in output order
         if (row == 0) return {ZEST_P_ALPHA, 0};
@@ -194,8 +202,13 @@ bool build_plan(const zest_mlp_desc &d, int precision, int order, MlpPlan *P, co
                     }
                     RowSrc rs = is_mod ? RowSrc{ZEST_P_PTS_BIAS, row} : row_src(param_of_rows_op, row);
                     if (feat < 0 || rs.param < 0) continue;
+                    // folded view layer: the trunk columns are the product Wc [W/2][W] in the scratch, the
+                    // direction columns stay those of views_linears.0 (col0 = W there)
+                    const bool folded_h = rs.param == kFoldSlot && sg.kind == SEG_H;
+                    const int param = rs.param == kFoldSlot && !folded_h ? (int)ZEST_P_VIEWS : rs.param;
+                    const int ldp = folded_h ? Wd : ld[param];
                     p.tile_src[((size_t)t * 64 + l) * spt + e] =
-                        ((uint32_t)rs.param << 24) | (uint32_t)(rs.row * ld[rs.param] + col0 + feat);
+                        ((uint32_t)param << 24) | (uint32_t)(rs.row * ldp + col0 + feat);
                 }
           }
     };

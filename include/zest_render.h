@@ -244,6 +244,31 @@ int zest_project_rays_bwd(const float *weights, const float *pts, const float *w
                           float focal, const float *grad_out, int R, int S, float *d_weights,
                           float *d_pts, void *stream);
 
+/* Scene-flow regularisers (reference losses.py:142-203 as train.py:480-510 calls them), values and
+ * gradients from one launch.  ref, post, prev, pp: [R,S,3] NDC points, contiguous; a tensor no
+ * requested term reads may be NULL.  With E = NDC2Euclidean (utils.py:507-514):
+ *   ZEST_SF_SMOOTH_*   mean over (R, s < n95 - 1, 3) of |F_s - F_{s+1}|, F = E(ref) - E(post | prev)
+ *   ZEST_SF_LKE_REF    0.5 mean over (R, s < n90, 3) of (E(post) - 2 E(ref) + E(prev))^2
+ *   ZEST_SF_LKE_CHAIN_BWD / _FWD   the same with (ref, post, prev) <- (prev, ref, pp) / (post, pp, ref)
+ * n95 = int(S * 0.95) and n90 = int(S * 0.9) are the caller's (the reference's slice lengths);
+ * scale_sp = 1 / (3 R (n95 - 1)) and scale_st = 1 / (3 R n90) are the means' denominators.
+ * loss_ray [R,2]: per-ray parts of (sum of the spatial terms, sum of the temporal terms), scaled;
+ * their column sums are the losses.  d_ref .. d_pp [R,S,3] or NULL: each receives, in full (zeros
+ * where no requested term reaches), d (w_sp * spatial + w_st * temporal) / d tensor.
+ * Errors: a term whose tensor is NULL, n95 < 2 with a spatial term, n90 < 1 with a temporal term,
+ * R < 1. */
+enum {
+    ZEST_SF_SMOOTH_REF_POST = 1,
+    ZEST_SF_SMOOTH_REF_PREV = 2,
+    ZEST_SF_LKE_REF = 4,
+    ZEST_SF_LKE_CHAIN_BWD = 8,
+    ZEST_SF_LKE_CHAIN_FWD = 16
+};
+int zest_sf_reg_fwd(const float *ref, const float *post, const float *prev, const float *pp, int terms,
+                    int R, int S, int n95, int n90, int H, int W, float focal, float scale_sp,
+                    float scale_st, float w_sp, float w_st, float *loss_ray, float *d_ref, float *d_post,
+                    float *d_prev, float *d_pp, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

@@ -329,6 +329,28 @@ class DistortionFn(Function):
         return grad * g, None
 
 
+class SceneFlowRegFn(Function):
+    """Scene-flow regularisers (csrc/sf_losses.hip): values and the gradients of w_sp * spatial + w_st * temporal with
+    respect to the point tensors from one HIP launch.  ref / post / prev / pp: [R,S,3] (None where no term reads the
+    tensor) -> (total, spatial, temporal); only `total` carries the graph."""
+
+    @staticmethod
+    def forward(ctx, ref, post, prev, pp, terms, H, W, focal, w_sp, w_st):
+        want = tuple(ctx.needs_input_grad[:4])                  # gradient buffers only where autograd asks for one
+        loss_ray, grads = zest_hip.sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp, w_st, want=want)
+        ctx.want = want
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        parts = loss_ray.sum(0)
+        sp, st = parts[0], parts[1]
+        ctx.mark_non_differentiable(sp, st)
+        return w_sp * sp + w_st * st, sp, st
+
+    @staticmethod
+    def backward(ctx, g, g_sp, g_st):
+        saved = iter(ctx.saved_tensors)
+        return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 6
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

@@ -24,7 +24,7 @@ import runpy
 import sys
 import types
 
-__all__ = ["install", "uninstall", "PATH_NAMES", "main"]
+__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -41,6 +41,8 @@ _REIMPORTED = {
     "networks": (("zest_utils", ("homo_warp", "build_rays", "build_rays_dy")), ("zest_renderer", ("rendering",))),
     "renderer": (("zest_utils", ("index_point_feature", "build_color_volume")),),
 }
+# opt-in (install(sf_losses=True) / ZEST_DROPIN_SF_LOSSES=1): the scene-flow regularisers, one HIP launch per call
+SF_LOSS_NAMES = ("compute_sf_smooth_loss", "compute_sf_lke_loss")
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -63,9 +65,12 @@ def _bind(mod, name, value):
     setattr(mod, name, value)
 
 
-def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True):
+def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
+            sf_losses=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
+    sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
+    they stay the caller's).
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +89,8 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
         targets[name] = target
     for name in modules:                                             # ... then rebind (uninstall() restores their own names)
         zest_name, names = PATH_NAMES[name]
+        if name == "losses" and sf_losses:
+            names = names + SF_LOSS_NAMES
         target = targets[name]
         zest = importlib.import_module(zest_name)
         for n in names:
@@ -113,10 +120,11 @@ def main(argv=None):
     if not argv or argv[0] in ("-h", "--help"):
         print("usage: python -m zest_dropin SCRIPT.py [script arguments]\n"
               "runs SCRIPT (e.g. the reference's train.py / test.py) with the MI355X rendering path bound into its "
-              "own networks / utils / renderer / losses modules")
+              "own networks / utils / renderer / losses modules; ZEST_DROPIN_SF_LOSSES=1 also binds the scene-flow "
+              "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
-    install(reference_dir=os.path.dirname(script))
+    install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

@@ -80,6 +80,7 @@ _SIGS = {
     "zest_distortion_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "zest_project_rays_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp]),
     "zest_project_rays_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i, _i, _vp, _vp, _vp]),
+    "zest_sf_reg_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -308,6 +309,44 @@ def project_rays_bwd(weights, pts, w2c, H, W, focal, grad_out, want_w=True, want
                                        _ptr(grad_out), R, S, _ptr(dw), _ptr(dp), _stream(weights)),
            "zest_project_rays_bwd")
     return dw, dp
+
+
+SF_SMOOTH_REF_POST, SF_SMOOTH_REF_PREV, SF_LKE_REF, SF_LKE_CHAIN_BWD, SF_LKE_CHAIN_FWD = 1, 2, 4, 8, 16
+SF_SPATIAL = SF_SMOOTH_REF_POST | SF_SMOOTH_REF_PREV
+SF_TEMPORAL = SF_LKE_REF | SF_LKE_CHAIN_BWD | SF_LKE_CHAIN_FWD
+
+
+def sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp=1.0, w_st=1.0, want=(True, True, True, True), grads=None):
+    """Scene-flow regularisers, one launch: ref / post / prev / pp [R,S,3] NDC points (None where no requested
+    term reads the tensor), terms a mask of SF_* -> (loss_ray [R,2]: per-ray parts of the spatial and the temporal
+    sum, already divided by the means' denominators; [d_ref, d_post, d_prev, d_pp]: d (w_sp * spatial + w_st *
+    temporal) / d tensor, [R,S,3] each, None where `want` is false or the tensor is None).  grads: optional
+    preallocated [R,S,3] fp32 tensors (or None) to write the gradients into; every row of them is written."""
+    ref = _dev(ref, "ref", (None, None, 3))
+    R, S = int(ref.shape[0]), int(ref.shape[1])
+    pts = [ref] + [_dev(t, n, (R, S, 3)) for t, n in ((post, "post"), (prev, "prev"), (pp, "pp"))]
+    n95, n90 = int(S * 0.95), int(S * 0.9)                      # the reference's slice lengths, its expressions
+    terms = int(terms)
+    if R < 1 or terms <= 0 or (terms & SF_SPATIAL and n95 < 2) or (terms & SF_TEMPORAL and n90 < 1):
+        raise RuntimeError("zest_hip: sf_reg needs R >= 1, a term, int(S * 0.95) >= 2 for a spatial and int(S * 0.9) >= 1 "
+                           "for a temporal term; got R=%d S=%d terms=0x%x" % (R, S, terms))
+    scale_sp = 1.0 / (3.0 * R * (n95 - 1)) if n95 >= 2 else 0.0
+    scale_st = 1.0 / (3.0 * R * n90) if n90 >= 1 else 0.0
+    out = []
+    for k in range(4):
+        g = None
+        if want[k] and pts[k] is not None:
+            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(pts[k])
+            if g.shape != pts[k].shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != ref.device:
+                raise RuntimeError("zest_hip: sf_reg gradient buffer %d must be a contiguous fp32 %s on %s"
+                                   % (k, tuple(pts[k].shape), ref.device))
+        out.append(g)
+    loss_ray = torch.empty(R, 2, device=ref.device, dtype=torch.float32)
+    _check(lib().zest_sf_reg_fwd(_ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]), terms, R, S, n95, n90,
+                                 int(H), int(W), float(focal), scale_sp, scale_st, float(w_sp), float(w_st),
+                                 _ptr(loss_ray), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                 _stream(ref)), "zest_sf_reg_fwd")
+    return loss_ray, out
 
 
 def nchw_to_nhwc(x):

@@ -252,8 +252,6 @@ __global__ __launch_bounds__(kThreads) void volume_from_cl_kernel(const float4 *
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int zest_encode_bwd(const float *g_x, const float *ndc, int R, int S, int has_time, float t,

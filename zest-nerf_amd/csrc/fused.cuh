@@ -176,11 +176,7 @@ __device__ __forceinline__ float4 zest_color_tap_fast(const float4 *__restrict__
     const float tx = fx - x0f, ty = fy - y0f;
     const int x0 = (int)x0f, y0 = (int)y0f;
     const int i00 = y0 * W + x0, dx = x0 + 1 < W ? 1 : 0, dy = y0 + 1 < H ? W : 0;
-#ifdef ZEST_EXPERIMENT_TAP_SAME
-    const float4 a = img[i00 & 0], b = img[(i00 + dx) & 0], d = img[(i00 + dy) & 0], e = img[(i00 + dy + dx) & 0];
-#else
     const float4 a = img[i00], b = img[i00 + dx], d = img[i00 + dy], e = img[i00 + dy + dx];
-#endif
     const float w00 = (1.0f - tx) * (1.0f - ty), w10 = tx * (1.0f - ty), w01 = (1.0f - tx) * ty, w11 = tx * ty;
     float4 o;
     o.x = fmaf(w11, e.x, fmaf(w01, d.x, fmaf(w10, b.x, w00 * a.x)));
@@ -216,28 +212,13 @@ __device__ __forceinline__ void encode_feat_operand(const FusedNet &n, const flo
 #pragma unroll
                 for (int j = 0; j < 3; j++) cam.k[i][j] = cl[12 + 3 * i + j];
             }
-#ifdef ZEST_EXPERIMENT_TAP_SAME        // timing experiment only: every tap reads pixel 0 of view 0 (arithmetic kept, memory trivial)
-            o = zest_color_tap<true>(n.imgs, n.H, n.W, cam, pw[0], pw[1], pw[2]);
-#else
             o = zest_color_tap(n.imgs + (size_t)vc * n.H * n.W, n.H, n.W, cam, pw[0], pw[1], pw[2]);
-#endif
         } else {
             o = zest_color_tap_fast(n.imgs + vc * (n.H * n.W), n.H, n.W, cl, pw[0], pw[1], pw[2]);
         }
         const bool on = view < n.V;
         dst[0] = on ? o.x : 0.f, dst[1] = on ? o.y : 0.f, dst[2] = on ? o.z : 0.f, dst[3] = on ? o.w : 0.f;
     };
-#ifdef ZEST_EXPERIMENT_NO_GATHER      // timing experiment only: features are zero
-    valid = false;
-#endif
-#ifdef ZEST_EXPERIMENT_FAKE_FEAT      // timing experiment only: no lookups, but feature values with realistic bit patterns
-    if (valid) {                      // (zero features let the chip hold a higher clock: not a clean knock-out)
-#pragma unroll
-        for (int i = 0; i < NK * 8; i++)
-            v[i] = __builtin_amdgcn_fractf(ndc[0] * (13.37f + (float)i) + ndc[2] * 7.1f + (float)grp * 0.31f) - 0.25f;
-    }
-    valid = false;
-#endif
     const int rv = feat_volume_round(n.V);
     if (valid) {
         float vv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -263,11 +244,7 @@ __device__ __forceinline__ void encode_feat_operand(const FusedNet &n, const flo
                 const int xc = min(max(xi, 0), n.Wv - 1), yc = min(max(yi, 0), n.Hv - 1),
                           zc = min(max(zi, 0), n.D - 1);
                 wgt[c] = ok ? (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty) * (dz ? tz : 1.0f - tz) : 0.0f;
-#ifdef ZEST_EXPERIMENT_TAP_SAME
-                tap[c] = n.vol[(((yc * n.Wv + xc) * n.D + zc) & 0) + grp];
-#else
                 tap[c] = n.vol[2 * ((yc * n.Wv + xc) * n.D + zc) + grp];      // zest_vox, 32-bit (checked by the host)
-#endif
             }
 #pragma unroll
             for (int c = 0; c < 8; c++) {
@@ -370,16 +347,6 @@ __device__ __forceinline__ float block_excl_prod(float f, int c, float *total) {
 #ifndef ZEST_FUSED_WG_PER_CU
 #define ZEST_FUSED_WG_PER_CU 1
 #endif
-// Register-pressure knobs of the two-net kernels (measured: tools/kernel_resources.py):
-#ifndef ZEST_REBUILD_PTS
-#define ZEST_REBUILD_PTS 0         // 1: the point operand is rebuilt from LDS at the skip layer instead of kept in registers
-#endif
-#ifndef ZEST_GATHER_FENCE
-#define ZEST_GATHER_FENCE 1        // 1: two-net kernels with two k-tiles of static features gather one column block at a time
-#endif
-#ifndef ZEST_EARLY_DYN_GATHER
-#define ZEST_EARLY_DYN_GATHER 0    // 1: the dynamic net's gathers are issued at the start of the pass, operand parked in LDS
-#endif
 // V2S: the static net is a 'v2' net (additive modulation; only single-net kernels with features are built for it)
 template <int EP, int NT_FEAT_S, bool DYN, int NT_FEAT_D, bool V2S = false>
 __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_CU / 4) void fused_blocks_kernel(FusedArgs a) {
@@ -389,38 +356,29 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
     // both nets are read from their inference streams (mlp_plan.h: feature_linear folded into the view layer)
     constexpr int UNITS_S = stream_units(4, NT_FEAT_S, NP, true), UNITS_D = DYN ? stream_units(6, NT_FEAT_D, NP, true) : 0;
     using Ring = RingTiles<kFusedWaves, UNITS_S, UNITS_D>;
-    // LDS: weight ring | cameras of both nets | per-lane (z, dist) of the pass's samples | ring flags |
-    // block records | sample coordinates (the point operand is rebuilt from them at the skip layer) |
-    // with a dynamic net: the static net's per-sample results and the dynamic feature operand, parked
-    // while the other net runs (registers the engine needs: the two-net kernels spilled them before)
-    constexpr int kFdBytes = (DYN && MOD_D && ZEST_EARLY_DYN_GATHER) ? kFusedWaves * CB * (NT_FEAT_D / 2) * NP * 1024 : 0;
+    // LDS: weight ring | cameras of both nets | per-lane (z, dist) of the pass's samples | an unused gap |
+    // block records | sample coordinates (the point operands are built from them) | with a dynamic net: the
+    // static net's per-sample results, parked while the dynamic net runs (registers the engine needs: the
+    // two-net kernels spilled them before) | the open ray's sums between two passes
     constexpr int kStBytes = DYN ? kFusedWaves * 32 * 24 : 0;
-    // modulation cache (mlp_engine.cuh ZEST_MCACHE_JB): kMcJB row blocks of m per wave, [row block][column block][lane] x 16 B;
-    // the two nets use it one after the other
-    constexpr bool kMc = mcache_for(EP, MOD_S, NT_FEAT_S / 2) || (DYN && mcache_for(EP, MOD_D, NT_FEAT_D / 2));
-    constexpr int kMcWaveBytes = kMc ? kMcJB * CB * 1024 : 0;
+    // Unused.  The gap keeps every later region at the LDS address the kernels were measured with; dropping it
+    // moves them all and wants a timing of its own.
+    constexpr int kGapBytes = 2 * kSlots * 4;
     __shared__ __attribute__((aligned(16))) char lds[kRingUnits * 1024 + 2 * kMaxViews * kCamStride * 4 +
-                                                     kFusedWaves * 32 * 8 + 2 * kSlots * 4 +
+                                                     kFusedWaves * 32 * 8 + kGapBytes +
                                                      kFusedWaves * kPartialFloats * 4 + kFusedWaves * 32 * 16 +
-                                                     kFdBytes + kStBytes + 2 * kCarryFloats * 4 +
-                                                     kFusedWaves * kMcWaveBytes];
+                                                     kStBytes + 2 * kCarryFloats * 4];
     static_assert(sizeof(lds) <= 163840, "LDS budget of one workgroup per CU");
-    static_assert((sizeof(lds) - kFusedWaves * kMcWaveBytes) % 16 == 0, "the modulation cache starts 16-byte aligned");
     float *cams_s = reinterpret_cast<float *>(lds + kRingUnits * 1024), *cams_d = cams_s + kMaxViews * kCamStride;
     float2 *zd_lds = reinterpret_cast<float2 *>(cams_d + kMaxViews * kCamStride);
     constexpr bool PROJ = EP != ZEST_PREC_F16X3;         // 16-bit operand modes: fast projection
     stage_cams<PROJ>(a.st, cams_s);
     if (DYN) stage_cams<PROJ>(a.dy, cams_d);
-    int *ring_flags = reinterpret_cast<int *>(zd_lds + kFusedWaves * 32);
-    float *rec_lds = reinterpret_cast<float *>(ring_flags + 2 * kSlots);      // [waves][kPartialFloats]
+    char *gap = reinterpret_cast<char *>(zd_lds + kFusedWaves * 32);
+    float *rec_lds = reinterpret_cast<float *>(gap + kGapBytes);                           // [waves][kPartialFloats]
     float4 *x_lds = reinterpret_cast<float4 *>(rec_lds + kFusedWaves * kPartialFloats);    // [waves][32]
-    uint4 *fd_lds = reinterpret_cast<uint4 *>(x_lds + kFusedWaves * 32);                   // [waves][CB][k-tile][part][64]
-    float2 *st_lds = reinterpret_cast<float2 *>(reinterpret_cast<char *>(fd_lds) + kFdBytes);   // [waves][3][32]
+    float2 *st_lds = reinterpret_cast<float2 *>(x_lds + kFusedWaves * 32);                 // [waves][3][32]
     float *carry_lds = reinterpret_cast<float *>(reinterpret_cast<char *>(st_lds) + kStBytes);  // [2][kCarryFloats]
-    char *mc_lds = lds + sizeof(lds) - kFusedWaves * kMcWaveBytes;                              // 16-byte aligned (sizes above)
-#ifdef ZEST_RING_FLAGS
-    Ring::init_flags(ring_flags);
-#endif
     __syncthreads();
 
     const int lane0 = threadIdx.x & 63;
@@ -428,15 +386,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
     const Ring tiles{lds, (gptr_u4)a.st.tiles, (gptr_u4)a.dy.tiles, lane0, lane0 >> 4, wave,
                      (unsigned)(wave * Ring::kPieces * 64 + lane0) * 16u,
                      (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds +
-                         (unsigned)wave * Ring::kPieces * 1024u
-#ifdef ZEST_RING_FLAGS
-                     , (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)ring_flags
-#endif
-    };
+                         (unsigned)wave * Ring::kPieces * 1024u};
     tiles.init_addr();
-    if constexpr (kMc)
-        tiles.init_mcache((unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)mc_lds +
-                          (unsigned)wave * kMcWaveBytes + (unsigned)lane0 * 16u);
     tiles.prologue();
 
     // The workgroup's blocks.  Workgroups are numbered so that those of one XCD (equal blockIdx % 8: one L2)
@@ -444,11 +395,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
     // render contiguous pixel runs) meet in one L2 instead of being fetched into all eight.
     const bool ranges = a.ray_ranges != 0;
     const int n_wg = (int)gridDim.x;
-#ifndef ZEST_NO_XCD_ORDER
     const int wg = n_wg % 8 == 0 ? (int)(blockIdx.x % 8) * (n_wg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-#else
-    const int wg = (int)blockIdx.x;
-#endif
     int range_b0, range_nb;                 // first block, number of blocks
     if (ranges) {
         range_b0 = (int)((long long)wg * a.R / n_wg) * a.bpr;
@@ -534,8 +481,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
         };
         // ---- the pass's samples: coordinates, depths and spacings go to LDS (the point operands and the
         // compositing read them from there: no global load - and no vmcnt wait that would drain the
-        // weight DMA - once the networks run); the feature gathers of BOTH nets are issued here, while
-        // nothing else needs the registers, and the dynamic net's finished operand is parked in LDS
+        // weight DMA - once the networks run); the static net's feature gathers are issued here, while
+        // nothing else needs the registers
         OpArr<NT_FEAT_S / 2, NP> feat_s[CB];
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
@@ -546,61 +493,43 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
                 x_lds[wave * 32 + 16 * cb + col] = make_float4(b.x[0], b.x[1], b.x[2], 0.0f);
             }
             if constexpr (MOD_S) encode_feat_operand<EP, NT_FEAT_S / 2>(a.st, cams_s, b.x, b.pw, grp, b.valid, feat_s[cb]);
-#if ZEST_GATHER_FENCE
-            // one column block's taps at a time: both in flight together (~190 registers of tap data with
-            // 8 source views) push the two-net kernels, which hold more state, into scratch
+            // two-net kernels with two k-tiles of static features: one column block's taps at a time.  Both in
+            // flight together (~190 registers of tap data with 8 source views) push these kernels, which hold
+            // more state, into scratch
             if constexpr (DYN && NT_FEAT_S >= 4) __builtin_amdgcn_sched_barrier(0);
-#endif
-            if constexpr (DYN && MOD_D && ZEST_EARLY_DYN_GATHER) {
-                OpArr<NT_FEAT_D / 2, NP> fd;
-                encode_feat_operand<EP, NT_FEAT_D / 2>(a.dy, cams_d, b.x, b.pw, grp, b.valid, fd);
-#pragma unroll
-                for (int t = 0; t < NT_FEAT_D / 2; t++)
-#pragma unroll
-                    for (int pt = 0; pt < NP; pt++)
-                        fd_lds[(((wave * CB + cb) * (NT_FEAT_D / 2) + t) * NP + pt) * 64 + lane] =
-                            __builtin_bit_cast(uint4, fd.t[pt][t]);
-            }
         }
         // point operand of a net from the parked coordinates (C = 3: xyz; 4: xyz + frame index)
-        auto pts_static = [&](OpArr<2, NP> (&o)[CB], int token) __attribute__((always_inline)) {
+        auto pts_static = [&](OpArr<2, NP> (&o)[CB]) __attribute__((always_inline)) {
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 int at = wave * 32 + 16 * cb + col;
-                asm volatile("" : "+v"(at) : "v"(token));          // not before `token` exists (see engine_forward)
+                asm volatile("" : "+v"(at));          // opaque: the address is computed here, at its use
                 const float4 xv = x_lds[at];
                 const float x4[4] = {xv.x, xv.y, xv.z, 0.0f};
-#ifdef ZEST_EXPERIMENT_NO_ENCODE        // timing experiment only
-#pragma unroll
-                for (int t = 0; t < 2; t++) o[cb].t[0][t] = bf16x8{(short)lane, 1, 2, 3, 4, 5, 6, 7};
-#else
                 encode_pe_operand<EP, 3, 10, 2>(x4, grp, o[cb]);
-#endif
             }
         };
-        auto pts_dynamic = [&](OpArr<3, NP> (&o)[CB], int token) __attribute__((always_inline)) {
+        auto pts_dynamic = [&](OpArr<3, NP> (&o)[CB]) __attribute__((always_inline)) {
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 int at = wave * 32 + 16 * cb + col;
-                asm volatile("" : "+v"(at) : "v"(token));
+                asm volatile("" : "+v"(at));
                 const float4 xv = x_lds[at];
                 const float x4[4] = {xv.x, xv.y, xv.z, a.frame_idx};
                 encode_pe_operand<EP, 4, 10, 3>(x4, grp, o[cb]);
             }
         };
         ZEST_STAMP(st_enc);
-        if constexpr (ZEST_REBUILD_PTS) {
-            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true, true>(tiles, unit, pts_static, feat_s,
-                                                        views_of(a.st, cams_s), head_s, rgb_s);
-        } else {
+        {
+            // built once and kept in registers through the net; the engine takes copies (layers 0 and 5)
             OpArr<2, NP> pts_keep[CB];
-            pts_static(pts_keep, 0);
-            auto pts_copy = [&](OpArr<2, NP> (&o)[CB], int) __attribute__((always_inline)) {
+            pts_static(pts_keep);
+            auto pts_copy = [&](OpArr<2, NP> (&o)[CB]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
             };
-            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true, true>(tiles, unit, pts_copy, feat_s,
-                                                        views_of(a.st, cams_s), head_s, rgb_s);
+            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true>(tiles, unit, pts_copy, feat_s,
+                                                                   views_of(a.st, cams_s), head_s, rgb_s);
         }
         ZEST_STAMP(st_eng);
         // ---- per-block compositing on lanes 0 .. BS-1 (sample = lane): rgb rows 0-2, head rows 0, 1
@@ -635,16 +564,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
                 st_lds[(wave * 3 + 2) * 32 + lane] = make_float2(blend_s, 0.0f);
             }
             OpArr<NT_FEAT_D / 2, NP> feat_d[CB];
-            if constexpr (MOD_D && ZEST_EARLY_DYN_GATHER) {
-#pragma unroll
-                for (int cbi = 0; cbi < CB; cbi++)
-#pragma unroll
-                    for (int t = 0; t < NT_FEAT_D / 2; t++)
-#pragma unroll
-                        for (int pt = 0; pt < NP; pt++)
-                            feat_d[cbi].t[pt][t] = __builtin_bit_cast(
-                                bf16x8, fd_lds[(((wave * CB + cbi) * (NT_FEAT_D / 2) + t) * NP + pt) * 64 + lane]);
-            } else if constexpr (MOD_D) {
+            if constexpr (MOD_D) {
                 // the dynamic net's gathers, now that the static net's registers are free (issued together
                 // with the static ones they push the gather phase into scratch)
 #pragma unroll
@@ -655,18 +575,15 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
                 }
             }
             ZEST_STAMP(st_comp);
-            if constexpr (ZEST_REBUILD_PTS) {
-                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true, true>(tiles, unit, pts_dynamic, feat_d,
-                                                            views_of(a.dy, cams_d), head_d, rgb_d);
-            } else {
+            {
                 OpArr<3, NP> pts_keep[CB];
-                pts_dynamic(pts_keep, 0);
-                auto pts_copy = [&](OpArr<3, NP> (&o)[CB], int) __attribute__((always_inline)) {
+                pts_dynamic(pts_keep);
+                auto pts_copy = [&](OpArr<3, NP> (&o)[CB]) __attribute__((always_inline)) {
 #pragma unroll
                     for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
                 };
-                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true, true>(tiles, unit, pts_copy, feat_d,
-                                                            views_of(a.dy, cams_d), head_d, rgb_d);
+                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true>(tiles, unit, pts_copy, feat_d,
+                                                                         views_of(a.dy, cams_d), head_d, rgb_d);
             }
             ZEST_STAMP(st_eng);
             const float2 s0 = st_lds[(wave * 3 + 0) * 32 + cbs], s1 = st_lds[(wave * 3 + 1) * 32 + cbs],
@@ -699,11 +616,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
                 o[i] = make_float4(rec[4 * i], rec[4 * i + 1], rec[4 * i + 2], rec[4 * i + 3]);
         }
         }   // g >= 0
-#ifdef ZEST_EXPERIMENT_NO_FINISH       // timing experiment only: no rendezvous, no ray finishing (results are wrong)
-        if (false) {
-#else
         if (ranges) {
-#endif
             // The pass holds consecutive blocks of the workgroup's rays.  After one rendezvous the wave with a
             // ray's first block OF THIS PASS chains that ray's records of this pass (80 B each, in LDS) - onto
             // the sums carried over from the previous pass if the ray began there (then it is wave 0) - and
@@ -723,14 +636,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
             }
         }
         ZEST_STAMP(st_comp);
-        tiles.next_pass();
     }
     tiles.drain();
-#ifdef ZEST_RING_FLAGS
-    if (tiles.poisoned && lane0 == 0) {
-        a.partials[0] = __builtin_nanf("");   // make a protocol failure visible
-    }
-#endif
 #ifdef ZEST_STAMPS
     if (a.stamps && lane0 == 0) {
         unsigned long long *o = a.stamps + (size_t)(blockIdx.x * kFusedWaves + wave) * 8;

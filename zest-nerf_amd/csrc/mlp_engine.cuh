@@ -32,7 +32,6 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float v4f;
 typedef __attribute__((ext_vector_type(4))) unsigned v4u;
 typedef const __attribute__((address_space(1))) v4u *gptr_u4;        // global memory, 16-byte units
-typedef __attribute__((address_space(3))) int lds_int;                // an int in LDS
 
 namespace zest {
 
@@ -67,9 +66,6 @@ constexpr int kChunk = ZEST_CHUNK, kSlots = ZEST_SLOTS, kRingUnits = kChunk * kS
 static_assert(kStreamAlign % kRingUnits == 0, "stream padding must be a multiple of the ring size");
 static_assert(kSlots >= kAhead + 1, "a slot is refilled while the previous chunk may still be read");
 
-#ifndef ZEST_DEFER_DMA
-#define ZEST_DEFER_DMA 0   // 1: weight DMA issued in the row-block epilogues instead of at the rendezvous (see flush())
-#endif
 #ifndef ZEST_ISSUERS
 #define ZEST_ISSUERS 8     // waves of the workgroup that issue the weight DMA (8: every wave its share; 4: waves 0-3,
 #endif                     // one per SIMD, take all of it and their SIMD partners 4-7 none - measured in DESIGN.md section 4)
@@ -84,11 +80,6 @@ struct RingTiles {
     int lane, grp, wave;   // grp = lane >> 4; wave: provably uniform (readfirstlane)
     unsigned voff;         // (wave * kPieces * 64 + lane) * 16: this lane's byte offset in a chunk
     unsigned lds_wave_base; // LDS byte address of the ring + wave * kPieces * 1024
-#ifdef ZEST_RING_FLAGS     // rendezvous-free ring: per-slot counters in LDS instead of a barrier per chunk
-    unsigned flags;        // LDS byte address of 2 * kSlots ints, see off_landed / off_done
-    mutable int gen_base = 0;      // ring generations completed by earlier passes of this workgroup
-    mutable int poisoned = 0;      // a bounded wait ran out (never in a correct run): results are invalid
-#endif
 #ifdef ZEST_STAMPS         // diagnostic build: cycles spent in enter_chunk (DMA wait + barrier + issue)
     mutable unsigned long long t_wait = 0, t_issue = 0, t_vm = 0;   // t_vm: the vmcnt part of t_wait
 #endif
@@ -125,187 +116,37 @@ struct RingTiles {
                          "global_load_lds_dwordx4 %0, %1 offset:3072"
                          :: "v"(voff), "s"(sb), "s"(dst) : "memory", "m0");
     }
-#ifdef ZEST_RING_FLAGS
-    // Two monotonic counters per slot, each bumped once per wave and use of the slot:
-    //   landed[s]: this wave's DMA pieces of the chunk now in slot s are in LDS (published one
-    //              chunk early, when the wave enters the chunk before it)
-    //   done[s]:   this wave has issued its last read of the chunk in slot s
-    // A wave may read chunk q once landed[q % kSlots] == NW * (generation(q) + 1), and may
-    // refill slot t once done[t] == NW * generation(new occupant).  landed[s] and the done
-    // counter the same enter_chunk needs (slot s + kAhead) sit next to each other: one 8-byte
-    // read.  No wave ever waits for the others to ARRIVE anywhere: the two waves of a SIMD
-    // drift apart and one's MFMAs cover the other's waits, DMA issue and epilogues.
-    static_assert(kSlots >= kAhead + 2, "flag ring: a slot is refilled while laggards read its neighbours");
-    static constexpr int off_landed(int slot) { return 8 * (slot % kSlots); }
-    static constexpr int off_done(int slot) { return 8 * ((slot % kSlots - kAhead + kSlots) % kSlots) + 4; }
-    static __device__ void init_flags(int *f) {             // before the workgroup's first barrier
-        if (threadIdx.x < 2 * kSlots) f[threadIdx.x] = 0;
-        __syncthreads();
-        // the very first enter_chunk "finishes" a chunk that never was: pre-charge its counter
-        if (threadIdx.x == 0) f[off_done(kSlots - 1) / 4] = -NW;
-    }
-    // The flag traffic is inline asm on purpose: a C++ wait loop in every enter_chunk puts ~80
-    // loops into the unrolled network, after which hipcc no longer keeps the operand arrays in
-    // registers; an asm block is straight-line code to it.  Lane 0 does the adds (EXEC = 1).
-    // No VGPR is first written inside an asm block: hipcc inserts no MFMA->VALU wait states for
-    // asm (cdna guide 5.7), and a scratch register it hands out may be the destination of an MFMA
-    // still in flight (seen: the adds after the last rgb MFMA added an activation instead of 1).
-    // Constants come in as inputs and the read targets are initialised in C++.
-    template <int OFF_A, int OFF_B>
-    __device__ __forceinline__ void bump2() const {
-        unsigned long long save;
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\t"
-                     "ds_add_u32 %2, %1 offset:%3\n\tds_add_u32 %2, %1 offset:%4\n\ts_mov_b64 exec, %0"
-                     : "=&s"(save) : "v"(1u), "v"(flags), "i"(OFF_A), "i"(OFF_B) : "memory");
-    }
     __device__ __forceinline__ void prologue() const {
 #pragma unroll
         for (int c = 0; c < kAhead; c++) issue(c);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"((kAhead - 1) * kPieces) : "memory");
-        unsigned long long save;
-        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\t"
-                     "ds_add_u32 %2, %1 offset:%3\n\ts_mov_b64 exec, %0"
-                     : "=&s"(save) : "v"(1u), "v"(flags), "i"(off_landed(0)) : "memory");
-    }
-    __device__ __forceinline__ void next_pass() const { gen_base += kChunks / kSlots; }
-    // The two counters a chunk entry checks are read kPreRead units ahead of it (pre_read), with
-    // the tile reads around them hiding the LDS latency; the check itself is then scalar work
-    // on registers.  Only if the early values are short of the targets does the wave fall into
-    // the (bounded) re-read loop.
-    static constexpr int kPreRead = 5;
-    typedef int v2i __attribute__((ext_vector_type(2)));
-    mutable v2i flag_pre = {0, 0};
-    __device__ __forceinline__ void pre_read(int chunk) const {
-        flag_pre = *(const volatile __attribute__((address_space(3))) v2i *)(flags + off_landed(chunk));
-    }
-    template <int OFF>
-    __device__ __forceinline__ void await(int need_l, int need_d) const {
-        unsigned va = (unsigned)flag_pre.x, vb = (unsigned)flag_pre.y;
-        int sa, sb, tries = 1 << 14;       // bounded: a protocol bug must not hang the GPU
-        asm volatile("0:\n\t"
-                     "v_readfirstlane_b32 %2, %0\n\t"
-                     "v_readfirstlane_b32 %3, %1\n\t"
-                     "s_nop 1\n\t"
-                     "s_cmp_ge_i32 %2, %6\n\t"
-                     "s_cselect_b32 %2, 1, 0\n\t"
-                     "s_cmp_ge_i32 %3, %7\n\t"
-                     "s_cselect_b32 %3, 1, 0\n\t"
-                     "s_and_b32 %2, %2, %3\n\t"
-                     "s_cbranch_scc1 1f\n\t"
-                     "s_sub_u32 %4, %4, 1\n\t"
-                     "s_cmp_eq_u32 %4, 0\n\t"
-                     "s_cbranch_scc1 1f\n\t"
-                     "s_sleep 1\n\t"
-                     "ds_read_b32 %0, %5 offset:%8\n\t"
-                     "ds_read_b32 %1, %5 offset:%9\n\t"
-                     "s_waitcnt lgkmcnt(0)\n\t"
-                     "s_branch 0b\n\t"
-                     "1:"
-                     : "+v"(va), "+v"(vb), "=&s"(sa), "=&s"(sb), "+s"(tries)
-                     : "v"(flags), "s"(need_l), "s"(need_d), "i"(OFF), "i"(OFF + 4)
-                     : "memory", "scc");
-        if (tries == 0) poisoned = 1;
     }
     __device__ __forceinline__ void enter_chunk(int chunk) const {
 #ifdef ZEST_STAMPS
         const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #endif
-        // own pieces of the NEXT chunk have landed (chunks chunk+2 .. chunk+kAhead-1 stay in flight);
-        // all reads of the previous chunk are issued (LDS operations of a wave execute in order)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"((kAhead - 2) * kPieces) : "memory");
-#ifdef ZEST_STAMPS
-        t_vm += __builtin_amdgcn_s_memtime() - t0;
-#endif
-        // (a switch, because the asm offsets must be literal constants; `chunk` is one only after
-        // unrolling - build with -mllvm -pragma-unroll-threshold raised, see build_hip.py)
-        const int need_l = NW * (gen_base + chunk / kSlots + 1), need_d = NW * (gen_base + (chunk + kAhead) / kSlots);
-        if (chunk % kChunks == 0) pre_read(chunk);           // first chunk of a pass: nothing ran ahead of it
-        switch (chunk % kSlots) {
-#define ZEST_CASE(S) case S: bump2<off_landed(S + 1), off_done(S + kSlots - 1)>(); await<off_landed(S)>(need_l, need_d); break;
-            ZEST_CASE(0) ZEST_CASE(1) ZEST_CASE(2) ZEST_CASE(3) ZEST_CASE(4) ZEST_CASE(5) ZEST_CASE(6) ZEST_CASE(7)
-            ZEST_CASE(8) ZEST_CASE(9) ZEST_CASE(10) ZEST_CASE(11) ZEST_CASE(12) ZEST_CASE(13) ZEST_CASE(14) ZEST_CASE(15)
-#undef ZEST_CASE
-        }
-        static_assert(kSlots <= 16, "extend the slot switch");
-#ifdef ZEST_STAMPS
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
-        issue(chunk + kAhead);
-#ifdef ZEST_STAMPS
-        t_wait += t1 - t0, t_issue += __builtin_amdgcn_s_memtime() - t1;
-#endif
-    }
-#else
-    __device__ __forceinline__ void prologue() const {
-#pragma unroll
-        for (int c = 0; c < kAhead; c++) issue(c);
-    }
-    __device__ __forceinline__ void next_pass() const {}
-    __device__ __forceinline__ void enter_chunk(int chunk) const {
-#ifdef ZEST_STAMPS
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
-        flush();
         // all but the youngest (kAhead-1)*kPieces of this wave's DMA pieces have landed
         asm volatile("s_waitcnt vmcnt(%0)" ::"i"((kAhead - 1) * kPieces) : "memory");
 #ifdef ZEST_STAMPS
         t_vm += __builtin_amdgcn_s_memtime() - t0;
 #endif
-#ifndef ZEST_EXPERIMENT_NO_BARRIER      // timing experiment only: results are wrong without it
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
 #ifdef ZEST_STAMPS
         const unsigned long long t1 = __builtin_amdgcn_s_memtime();
 #endif
-#ifndef ZEST_EXPERIMENT_NO_DMA          // timing experiment only
-#if ZEST_DEFER_DMA
-        pending = chunk + kAhead;               // issued by the next flush(): a layer's epilogue
-#else
         issue(chunk + kAhead);
-#endif
-#endif
 #ifdef ZEST_STAMPS
         t_wait += t1 - t0, t_issue += __builtin_amdgcn_s_memtime() - t1;
 #endif
     }
-#endif
-    // ZEST_DEFER_DMA: the refill of the slot a rendezvous frees is not issued at the rendezvous - in the middle
-    // of a run of MFMAs and tile reads, where an LDS-DMA piece holds the wave's issue for 100+ cycles
-    // (MI355X_MICROARCH.md, row 'LDS-DMA piece issue cost') - but at the next row block's epilogue, among plain
-    // VALU instructions.  `pending` is a compile-time constant at every use once the network is unrolled (it is -1
-    // again at the end of a net's stream, so also around the pass loop).  The counted vmcnt of enter_chunk is
-    // unchanged: a refill still pending at the next rendezvous is issued there, in front of the wait.
-    mutable int pending = -1;
-    __device__ __forceinline__ void flush() const {
-#if ZEST_DEFER_DMA
-#ifdef ZEST_STAMPS
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
-        if (pending >= 0) issue(pending);
-        pending = -1;
-#ifdef ZEST_STAMPS
-        t_issue += __builtin_amdgcn_s_memtime() - t1;
-#endif
-#endif
-    }
     __device__ __forceinline__ void touch(int unit) const {
         if (unit % kChunk == 0) enter_chunk(unit / kChunk);
-#ifdef ZEST_RING_FLAGS
-        if (unit % kChunk == kChunk - kPreRead) pre_read(unit / kChunk + 1);
-#endif
     }
     // LDS read addresses: exactly two base registers per access pattern (lower / upper 64 KiB of
     // the ring, the reach of the 16-bit DS offset field), made opaque once.  Left to itself hipcc
     // materialises every `const + lane * 16` beyond the first 64 KiB as a loop-invariant VGPR of
     // its own: ~60 registers of addresses that crowd out operands and end in scratch.
     mutable unsigned rd_lo = 0, rd_hi = 0, rb_lo = 0, rb_hi = 0;
-    // modulation cache (ZEST_MCACHE_JB, engine_layer): LDS byte address of this lane's 16 bytes in the wave's region
-    mutable unsigned mc = 0;
-    __device__ __forceinline__ void init_mcache(unsigned lds_addr) const {
-        mc = lds_addr;
-        asm volatile("" : "+v"(mc));
-    }
     __device__ __forceinline__ void init_addr() const {
         const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)ring;
         rd_lo = base + lane * 16, rd_hi = rd_lo + 65536, rb_lo = base + grp * 16, rb_hi = rb_lo + 65536;
@@ -318,11 +159,7 @@ struct RingTiles {
     }
     __device__ __forceinline__ bf16x8 load(int unit) const {
         touch(unit);
-#ifdef ZEST_EXPERIMENT_NO_LDSREAD       // timing experiment only: one read per chunk
-        const int r = unit / kChunk * kChunk % kRingUnits;
-#else
         const int r = unit % kRingUnits;
-#endif
         const v4u v = *lds_at<v4u>((r < 64 ? rd_lo : rd_hi) + (r % 64) * 1024);
         return *reinterpret_cast<const bf16x8 *>(&v);
     }
@@ -334,13 +171,7 @@ struct RingTiles {
     // walk the padding [unit, end) of a net's stream so every chunk is entered exactly once
     __device__ __forceinline__ void finish(int unit, int end) const {
 #pragma unroll
-        for (int u = (unit + kChunk - 1) / kChunk * kChunk; u < end; u += kChunk) {
-#ifdef ZEST_RING_FLAGS
-            pre_read(u / kChunk);
-#endif
-            enter_chunk(u / kChunk);
-        }
-        flush();
+        for (int u = (unit + kChunk - 1) / kChunk * kChunk; u < end; u += kChunk) enter_chunk(u / kChunk);
     }
     __device__ __forceinline__ void drain() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 };
@@ -433,9 +264,6 @@ __device__ __forceinline__ void store_tile(const float (&v)[8], OpArr<N, ep_part
 // Same bits as relu-then-round (rounding keeps the sign; -0 becomes +0 either way).  The engine's issue port
 // is the contended resource (MI355X_MICROARCH.md, row 'vector-instruction ISSUE cost': a 16x16x32 MFMA leaves
 // room for two plain VALU instructions): this takes 8 of the ~33 VALU instructions of a 256-wide row block away.
-#ifndef ZEST_PACKED_RELU
-#define ZEST_PACKED_RELU 1
-#endif
 typedef __attribute__((ext_vector_type(2))) short s16x2_t;
 __device__ __forceinline__ unsigned relu_bf16x2(unsigned u) {
     const s16x2_t r = __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, u), s16x2_t{0, 0});
@@ -459,34 +287,6 @@ __device__ __forceinline__ void engine_fp16_overflow_clamp() {
 #define ZEST_PREFETCH 3        // weight tiles kept in flight ahead of the MFMAs that consume them
 #endif
 constexpr int kPrefetch = ZEST_PREFETCH;
-
-// Modulation cache.  m = pts_bias(features) is the same in all eight trunk layers; the engine recomputes it per
-// row block and layer with 2 NKF extra MFMA pairs because 256 values per sample have no room in registers.  A kernel
-// built with ZEST_MCACHE_JB = n > 0 (the fused feature kernels whose ring is 64 KiB: fused.cuh) keeps the first n
-// row blocks of m in LDS instead, rounded to the operand type: layer 0 computes them as before and stores them (one
-// ds_write_b128 per column block), layers 1-7 skip those row blocks' modulation tiles - their stream units are
-// walked (touch) but neither read nor multiplied - and read m back (one ds_read_b128 per column block, unpacked
-// with two integer ops per pair).  With two feature k-tiles that removes 8 of the 40 MFMAs and 4 of the 20 tile
-// reads of a cached row block; with one k-tile the unpacking costs what the 4 MFMAs did, so only nets with
-// NKF >= 2 take it.  MC: 0 = off, 1 = compute + store (layer 0), 2 = load (layers 1-7).
-#ifndef ZEST_MCACHE_JB
-#define ZEST_MCACHE_JB 0
-#endif
-constexpr int kMcJB = ZEST_MCACHE_JB;
-constexpr bool mcache_for(int EP, bool mod, int nkf) { return kMcJB > 0 && mod && nkf >= 2 && EP != ZEST_PREC_F16X3; }
-
-template <int EP>
-__device__ __forceinline__ void unpack_pairs(const v4u q, float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        if constexpr (EP == ZEST_PREC_BF16) {
-            v[2 * i] = __uint_as_float(q[i] << 16), v[2 * i + 1] = __uint_as_float(q[i] & 0xFFFF0000u);
-        } else {
-            const f32x2_t f = __builtin_convertvector(__builtin_bit_cast(f16x2_t, q[i]), f32x2_t);
-            v[2 * i] = f[0], v[2 * i + 1] = f[1];
-        }
-    }
-}
 
 // What is fetched ahead for one row block: its bias initialisers and its first tiles.
 template <int NP>
@@ -518,7 +318,7 @@ struct NoSink {
 // 2 880 MFMAs, on the port the engine is short of (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost') - and a
 // scalar branch per row block cuts the unrolled network into basic blocks the register allocator answers with
 // ~200 spills.
-template <int EP, int CB, int NJB, int NKA, int NKB, bool MOD, int NKF, bool RELU, int MODE, bool V2, int MC, class Tiles,
+template <int EP, int CB, int NJB, int NKA, int NKB, bool MOD, int NKF, bool RELU, int MODE, bool V2, class Tiles,
           class Sink = NoSink>
 __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
                                              const OpArr<NKA, ep_parts(EP)> (&opa)[CB],
@@ -531,33 +331,25 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
     constexpr int NM = MOD ? 2 * NKF : 0, T = NM + 2 * (NKA + NKB);     // tiles per row block
     static_assert(T >= 1, "empty layer");
     // a sink wants the activated fp32 values: only the plain inference layer rounds first
-    constexpr bool kPackedRelu = ZEST_PACKED_RELU && RELU && MODE == 0 && EP != ZEST_PREC_F16X3 && __is_same(Sink, NoSink);
-    static_assert(MC == 0 || (MOD && MODE == 0 && NJB == 8), "the modulation cache serves modulated trunk layers");
-    // first tile a row block executes: its modulation tiles are skipped where m comes from the cache
-    auto k0_of = [](int jb) { return (MC == 2 && jb < kMcJB) ? NM : 0; };
-    auto preload = [&](RowBlockPre<NP> &p, int u0, int k0) {    // u0: the row block's header unit
+    constexpr bool kPackedRelu = RELU && MODE == 0 && EP != ZEST_PREC_F16X3 && __is_same(Sink, NoSink);
+    auto preload = [&](RowBlockPre<NP> &p, int u0) {            // u0: the row block's header unit
 #pragma unroll
         for (int rt = 0; rt < 2; rt++) {
             p.bias[rt] = tiles.load_bias(u0, 0, rt);
-            if (MOD && k0 == 0) p.mbias[rt] = tiles.load_bias(u0, 1, rt);
+            if (MOD) p.mbias[rt] = tiles.load_bias(u0, 1, rt);
         }
 #pragma unroll
-        for (int k = 0; k < k0; k++)                            // skipped units: the ring's chunks are still entered in order
-#pragma unroll
-            for (int pt = 0; pt < NP; pt++) tiles.touch(u0 + 1 + NP * k + pt);
-#pragma unroll
         for (int k = 0; k < kPrefetch; k++)
-            if (k0 + k < T) {
+            if (k < T) {
 #pragma unroll
-                for (int pt = 0; pt < NP; pt++) p.win[k][pt] = tiles.load(u0 + 1 + NP * (k0 + k) + pt);
+                for (int pt = 0; pt < NP; pt++) p.win[k][pt] = tiles.load(u0 + 1 + NP * k + pt);
             }
     };
     RowBlockPre<NP> pre;
-    preload(pre, unit, k0_of(0));
+    preload(pre, unit);
 #pragma unroll
     for (int jb = 0; jb < NJB; jb++) {
-        const int u0 = unit, k0 = k0_of(jb);
-        const bool mc_rd = MC == 2 && jb < kMcJB, mc_wr = MC == 1 && jb < kMcJB;
+        const int u0 = unit;
         // acc: the hi*hi products (all products of the one-part types); corr: hi*lo + lo*hi, scaled 2^11
         f32x4 acc[2][CB], macc[2][CB], corr[2][CB], mcorr[2][CB];
         bf16x8 win[kPrefetch][NP];
@@ -570,14 +362,14 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
                 acc[rt][cb] = pre.bias[rt];
-                if (MOD && !mc_rd) macc[rt][cb] = pre.mbias[rt];
+                if (MOD) macc[rt][cb] = pre.mbias[rt];
                 if (X3) corr[rt][cb] = f32x4{0.f, 0.f, 0.f, 0.f}, mcorr[rt][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
 #pragma unroll
-        for (int k = k0; k < T; k++) {
+        for (int k = 0; k < T; k++) {
             bf16x8 a[NP];
 #pragma unroll
-            for (int pt = 0; pt < NP; pt++) a[pt] = win[(k - k0) % kPrefetch][pt];
+            for (int pt = 0; pt < NP; pt++) a[pt] = win[k % kPrefetch][pt];
             const int rt = k % 2, kt = (k < NM ? k : k - NM) / 2;          // compile-time after unrolling
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
@@ -604,20 +396,11 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
             }
             if (k + kPrefetch < T) {
 #pragma unroll
-                for (int pt = 0; pt < NP; pt++) win[(k - k0) % kPrefetch][pt] = tiles.load(u0 + 1 + NP * (k + kPrefetch) + pt);
+                for (int pt = 0; pt < NP; pt++) win[k % kPrefetch][pt] = tiles.load(u0 + 1 + NP * (k + kPrefetch) + pt);
             }
-#ifdef ZEST_SCHED_PIN
-            __builtin_amdgcn_sched_barrier(0);      // keep the hand-made read-ahead distance
-#endif
-        }
-        v4u mq[CB];
-        if (mc_rd) {                                             // in flight while the last MFMAs drain
-#pragma unroll
-            for (int cb = 0; cb < CB; cb++) mq[cb] = *Tiles::template lds_at<v4u>(tiles.mc + (jb * CB + cb) * 1024);
         }
         unit = u0 + 1 + NP * T;
-        if (jb + 1 < NJB) preload(pre, unit, k0_of(jb + 1));                   // in flight during the epilogue
-        tiles.flush();
+        if (jb + 1 < NJB) preload(pre, unit);                   // in flight during the epilogue
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
             float v[8];
@@ -628,22 +411,10 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
             }
             if (MOD) {
                 float mv[8];
-                if (mc_rd) {
-                    unpack_pairs<EP>(mq[cb], mv);
-                } else {
 #pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        mv[i] = macc[i >> 2][cb][i & 3];
-                        if (X3) mv[i] = fmaf(mcorr[i >> 2][cb][i & 3], kLoUnscale, mv[i]);
-                    }
-                }
-                if (mc_wr) {
-                    if constexpr (!X3) {
-                        const uint4 q = make_uint4(pack_pair<EP>(mv[0], mv[1]), pack_pair<EP>(mv[2], mv[3]),
-                                                   pack_pair<EP>(mv[4], mv[5]), pack_pair<EP>(mv[6], mv[7]));
-                        *(__attribute__((address_space(3))) v4u *)(uintptr_t)(tiles.mc + (jb * CB + cb) * 1024) =
-                            __builtin_bit_cast(v4u, q);
-                    }
+                for (int i = 0; i < 8; i++) {
+                    mv[i] = macc[i >> 2][cb][i & 3];
+                    if (X3) mv[i] = fmaf(mcorr[i >> 2][cb][i & 3], kLoUnscale, mv[i]);
                 }
 #pragma unroll
                 for (int i = 0; i < 8; i++) v[i] = V2 ? v[i] + mv[i] : v[i] * mv[i];
@@ -666,53 +437,52 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
 // The whole network for CB column blocks of 16 samples, reading the stream from unit `unit` on
 // (advanced to the end of the net's padded stream).  pts/feat: encoder operands in plan position
 // order, NU_* = their logical stream tiles per row block = 2 x k-tiles.  `pts_fn(pts)` builds the
-// point operand; it is called twice, `pts_fn(pts, token)`, for layer 0 and for the skip layer 5, so
-// the operand does not occupy registers through layers 1-4 (a caller that prefers to keep it hands
-// out copies);
-// `views_fn(views)` builds the direction operand when it is first needed (op 10).  Results per column block: head (lane group g: rows 4g .. 4g+3 of the head
+// point operand.  It is called twice, for layer 0 and for the skip layer 5, each time into an operand that
+// lives for that layer only, so the engine holds no point operand of its own through layers 1-4.  Keep the
+// two calls: the standalone kernel (mlp_engine.hip) relies on them to have those registers free in between,
+// and the callers (all of which build the operand once and hand out copies) are tuned to this shape.
+// `views_fn(views)` builds the direction operand when it is first needed (op 10).
+// Results per column block: head (lane group g: rows 4g .. 4g+3 of the head
 // tile; row 0 alpha, rows 1.. extra heads) and rgb (group 0: rows 0-2), raw.
 // FOLD: the stream is the inference stream (mlp_plan.h): no feature_linear layer (sink id 8 is never seen), the
 // view layer multiplies the trunk output itself.  The training forward, whose backward needs the feature_linear
 // output in the stash, runs FOLD = false on the plain stream.
-template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool MCACHE = false, bool FOLD = false, class Tiles,
+template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool FOLD = false, class Tiles,
           class PtsFn, class ViewsFn, class Sink = NoSink>
 __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, PtsFn pts_fn,
                                                const OpArr<NU_FEAT / 2, ep_parts(EP)> (&feat)[CB], ViewsFn views_fn,
                                                f32x4 (&head)[CB], f32x4 (&rgb)[CB], const Sink &sink = Sink()) {
     constexpr int KP = NU_PTS / 2, KF = NU_FEAT / 2, NP = ep_parts(EP);
     static_assert(NU_PTS % 2 == 0 && NU_FEAT % 2 == 0, "units per row block come in row-tile pairs");
-    constexpr int MC0 = (MCACHE && mcache_for(EP, MOD, KF)) ? 1 : 0, MCL = MC0 ? 2 : 0;   // layer 0 stores m, 1-7 load it
     OpArr<8, NP> hA[CB], hB[CB];
     OpArr<0, NP> none[CB];
     f32x4 unused[CB];
     const int unit0 = unit;
     {
         OpArr<KP, NP> pts[CB];
-        pts_fn(pts, 0);
-        engine_layer<EP, CB, 8, KP, 0, MOD, KF, true, 0, V2, MC0>(tiles, unit, pts, none, feat, hA, unused, 0, sink);
+        pts_fn(pts);
+        engine_layer<EP, CB, 8, KP, 0, MOD, KF, true, 0, V2>(tiles, unit, pts, none, feat, hA, unused, 0, sink);
     }
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hA, none, feat, hB, unused, 1, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hB, none, feat, hA, unused, 2, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hA, none, feat, hB, unused, 3, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hB, none, feat, hA, unused, 4, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 1, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 2, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 3, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 4, sink);
     {
-        // `token` is a value layer 4 has just produced: a builder that ties its address arithmetic to it
-        // cannot be scheduled ahead of layers 1-4 (where its registers would be live all along)
         OpArr<KP, NP> pts[CB];
-        pts_fn(pts, (int)hA[CB - 1].t[0][7][0]);
-        engine_layer<EP, CB, 8, KP, 8, MOD, KF, true, 0, V2, MCL>(tiles, unit, pts, hA, feat, hB, unused, 5, sink);
+        pts_fn(pts);
+        engine_layer<EP, CB, 8, KP, 8, MOD, KF, true, 0, V2>(tiles, unit, pts, hA, feat, hB, unused, 5, sink);
     }
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hB, none, feat, hA, unused, 6, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, MCL>(tiles, unit, hA, none, feat, hB, unused, 7, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 6, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 7, sink);
     // trunk output in hB
-    engine_layer<EP, CB, 1, 8, 0, false, KF, false, 1, V2, 0>(tiles, unit, hB, none, feat, hA, head);
+    engine_layer<EP, CB, 1, 8, 0, false, KF, false, 1, V2>(tiles, unit, hB, none, feat, hA, head);
     if constexpr (!FOLD)
-        engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2, 0>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
+        engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
     // view layer: on the feature_linear output (hA -> hB), or folded on the trunk output itself (hB -> hA)
     OpArr<8, NP> (&vin)[CB] = FOLD ? hB : hA, (&vout)[CB] = FOLD ? hA : hB;
     OpArr<1, NP> views[CB];
     views_fn(views);
-    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2, 0>(tiles, unit, vin, views, feat, vout, unused, 9, sink);
+    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2>(tiles, unit, vin, views, feat, vout, unused, 9, sink);
     // rgb: 128 hidden features = first 4 k-tiles of the view layer's output
     OpArr<4, NP> h128[CB];
 #pragma unroll
@@ -721,7 +491,7 @@ __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, Pt
         for (int pt = 0; pt < NP; pt++)
 #pragma unroll
             for (int k = 0; k < 4; k++) h128[cb].t[pt][k] = vout[cb].t[pt][k];
-    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2, 0>(tiles, unit, h128, none, feat, vin, rgb);
+    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2>(tiles, unit, h128, none, feat, vin, rgb);
     tiles.finish(unit, unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD));
     unit = unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD);
 }

@@ -23,11 +23,7 @@ constexpr int mlp_cb(int EP) { return EP == ZEST_PREC_F16X3 ? 1 : 2; }
 //                                                          64 + k-tile feature_linear, 72 + k-tile view layer
 //   masks  [block][kStashMasks][CB][64 lanes] x 8 B       bit 8 * k-tile + element; 0-7 trunk, 8 view layer
 __device__ __forceinline__ void stash_store(uint4 *p, uint4 q) {
-#ifndef ZEST_STASH_CACHED              // (defined: plain stores, for A/B timing)
     __builtin_nontemporal_store(__builtin_bit_cast(v4u, q), reinterpret_cast<v4u *>(p));
-#else
-    *p = q;
-#endif
 }
 
 template <int CB>
@@ -64,22 +60,14 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
     constexpr int NP = ep_parts(EP), CB = mlp_cb(EP), UNITS = stream_units(NT_PTS, MOD ? NT_FEAT : 0, NP, FOLD);
     using Ring = RingTiles<kMlpWaves, UNITS, 0>;
     if constexpr (EP == ZEST_PREC_F16) engine_fp16_overflow_clamp();
+    // (the 2 * kSlots words behind the ring are unused: they keep the kernel's LDS size as it was measured)
     __shared__ __attribute__((aligned(16))) char lds[kRingUnits * 1024 + 2 * kSlots * 4];
-#ifdef ZEST_RING_FLAGS
-    int *ring_flags = reinterpret_cast<int *>(lds + kRingUnits * 1024);
-    Ring::init_flags(ring_flags);
-    __syncthreads();
-#endif
     const int lane = threadIdx.x & 63, col = lane & 15, grp = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const Ring tiles{lds, (gptr_u4)tiles_g, (gptr_u4)tiles_g, lane, grp, wave,
                      (unsigned)(wave * Ring::kPieces * 64 + lane) * 16u,
                      (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds +
-                         (unsigned)wave * Ring::kPieces * 1024u
-#ifdef ZEST_RING_FLAGS
-                     , (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)ring_flags
-#endif
-    };
+                         (unsigned)wave * Ring::kPieces * 1024u};
     tiles.init_addr();
     tiles.prologue();
     const int n_blocks = (M + 16 * CB - 1) / (16 * CB), n_pass = (n_blocks + kMlpWaves - 1) / kMlpWaves;
@@ -93,11 +81,7 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
         for (int cb = 0; cb < CB; cb++) {
             const long long m = m_base + 16 * cb + col;
             const bool valid = m < M;
-#ifdef ZEST_EXP_NO_XGATHER             // timing experiment only: every lane reads row 0 (one cache line set, L1 hits)
-            const float *xrow = x;
-#else
             const float *xrow = x + (size_t)(valid ? m : 0) * C_in;
-#endif
             load_pe_operand<EP, NT_PTS == 4 ? 3 : 4, 10, NT_PTS / 2>(xrow, valid, grp, pts[cb]);
             if (MOD) load_feat_operand<EP, NT_FEAT / 2>(xrow + P, F, valid, grp, feat[cb]);
             if constexpr (TRAIN) {          // the encoder's operands go to the stash too: inputs of the weight kernel
@@ -125,15 +109,15 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
         int unit = 0;
         // the rows of x come from global memory: the point operand is built once and kept (a reload in
         // the middle of the engine would drain the weight DMA behind its vmcnt wait)
-        auto pts_fn = [&](OpArr<NT_PTS / 2, NP> (&o)[CB], int) {
+        auto pts_fn = [&](OpArr<NT_PTS / 2, NP> (&o)[CB]) {
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) o[cb] = pts[cb];
         };
         if constexpr (TRAIN) {
             const StashSink<CB> sink{stash_tiles, stash_masks, (long long)pass * kMlpWaves + wave, lane, {}, {}};
-            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, false, false>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt, sink);
+            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, false>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt, sink);
         } else {
-            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, false, true>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt);
+            engine_forward<EP, CB, NT_PTS, MOD, NT_FEAT, V2, true>(tiles, unit, pts_fn, feat, views_fn, headt, rgbt);
         }
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
@@ -156,7 +140,6 @@ __global__ __launch_bounds__(kMlpWaves * 64, kMlpWaves / 4) void mlp_engine_kern
                 o[11] = zest_sigmoid(headt[cb][0]);                                                      // row 8
             }
         }
-        tiles.next_pass();
     }
     tiles.drain();
 }

@@ -60,13 +60,9 @@ Sizes sizes_of(int M) {
 }
 
 // a stash tile, read once by the kernel: streaming load (finishing kernel 323 -> 283 us, weight kernel 371 -> 353 us
-// against plain loads, -DZEST_STASH_CACHED)
+// against plain loads)
 __device__ __forceinline__ uint4 stash_load(const uint4 *p) {
-#ifndef ZEST_STASH_CACHED
     return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p)));
-#else
-    return *p;
-#endif
 }
 
 __device__ __forceinline__ void unpack8(const uint4 q, float (&v)[8]) {
@@ -161,11 +157,7 @@ struct MaskEpi {
 #pragma unroll
         for (int i = 0; i < 8; i++) v[i] = ((bits >> i) & 1u) ? v[i] * m[i] : 0.0f;
         // streaming store (the gradient stash is read back by the finishing and weight kernels only: data kernel 296 -> 248 us)
-#ifndef ZEST_STASH_CACHED              // (defined: plain stores, for A/B timing)
         __builtin_nontemporal_store(__builtin_bit_cast(v4u, pack8(v)), reinterpret_cast<v4u *>(&grad[((tile0 + jb) * CB + cb) * 64 + lane]));
-#else
-        grad[((tile0 + jb) * CB + cb) * 64 + lane] = pack8(v);
-#endif
     }
     __device__ __forceinline__ void rows(int, int, const float (&)[8]) const {}
 };
@@ -194,6 +186,7 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_data_kernel(
     constexpr int CB = 2, KP = NT_PTS / 2, KF = NT_FEAT / 2;
     constexpr int UNITS = bwd_stream_units(NT_PTS, MOD ? NT_FEAT : 0);
     using Ring = RingTiles<kWaves, UNITS, 0>;
+    // (the 2 * kSlots words behind the ring are unused: they keep the kernel's LDS size as it was measured)
     __shared__ __attribute__((aligned(16))) char lds[kRingUnits * 1024 + 2 * kSlots * 4];
     const int lane = threadIdx.x & 63, col = lane & 15, grp = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -273,7 +266,6 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_data_kernel(
         bwd_layer<CB, 8, 8, 0, MOD, KF, 0>(tiles, unit, ga, none, feat, gb, mask_epi(0, 0));      // layer 1 -> d pre_0
         bwd_layer<CB, KP, 8, 0, false, KF, 2>(tiles, unit, gb, none, feat, ga, pe0);               // layer 0: points
         tiles.finish(unit, UNITS);
-        tiles.next_pass();
     }
     tiles.drain();
 }
@@ -305,9 +297,6 @@ __device__ __forceinline__ int feat_col_of(int jb, int rt, int r, int grp, int V
 //     h_l = pre_l m, so the product is d h_l mask pre_l) becomes gradient tiles 78 .. 85 for the weight kernel,
 //     and d features = Wm^T d m (MFMA with the backward stream's tail) goes to the feature columns of g_x.
 template <int NT_PTS, int NT_FEAT>
-#ifdef ZEST_FIN_WAVES                  // occupancy experiment: cap the registers for this many waves per SIMD
-__attribute__((amdgpu_waves_per_eu(ZEST_FIN_WAVES, ZEST_FIN_WAVES)))
-#endif
 __global__ __launch_bounds__(256) void train16_finish_kernel(
     const float *__restrict__ x, int M, int P, int F, int C_in, const uint4 *__restrict__ bwd_tail,
     const uint4 *__restrict__ stash, uint4 *__restrict__ grad,
@@ -340,11 +329,7 @@ __global__ __launch_bounds__(256) void train16_finish_kernel(
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int c = pe_col_of<NT_PTS == 4 ? 3 : 4, 10>(jb, rt, r, grp);
-#ifdef ZEST_FIN_EXP_NO_GX               // timing experiment only
-                    if (c >= 0 && v[r] == 123456.0f) gx_row[cb][c] = v[r];
-#else
                     if (c >= 0) gx_row[cb][c] = v[r];
-#endif
                 }
             }
     if constexpr (KF > 0) {
@@ -416,11 +401,7 @@ __global__ __launch_bounds__(256) void train16_finish_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int c = feat_col_of(jb, rt, r, grp, (F - 8) / 4);
-#ifdef ZEST_FIN_EXP_NO_GX               // timing experiment only
-                        if (c >= 0 && acc[rt][cb][r] == 123456.0f) gx_row[cb][P + c] = acc[rt][cb][r];
-#else
                         if (c >= 0) gx_row[cb][P + c] = acc[rt][cb][r];
-#endif
                     }
             }
         }

@@ -11,14 +11,9 @@ using namespace zest;
 constexpr int EP = ZEST_PREC_BF16;
 constexpr int kWaves = 8;
 
-// a stash tile, read once by the kernel: streaming load (weight kernel 371 -> 353 us against plain loads,
-// -DZEST_STASH_CACHED)
+// a stash tile, read once by the kernel: streaming load (weight kernel 371 -> 353 us against plain loads)
 __device__ __forceinline__ uint4 stash_load(const uint4 *p) {
-#ifndef ZEST_STASH_CACHED
     return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p)));
-#else
-    return *p;
-#endif
 }
 
 // ------------------------------------------------------------------------------ weight kernel
@@ -83,9 +78,6 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_dw_kernel(
     // block b + 1 are requested before block b is computed, so their HBM latency hides behind the MFMAs
     const int items = (n_out + n_in) * CB;
     auto fetch_item = [&](long long b, int it) {
-#ifdef ZEST_DW_EXP_NO_LOADS            // timing experiment only: every block reads the first one again (L2 hits)
-        b = b0;
-#endif
         const int t = it / CB, cb = it % CB;
         const bool is_out = t < n_out;
         const int kt = is_out ? t : t - n_out;
@@ -121,16 +113,11 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_dw_kernel(
                 const int t = it / CB, cb = it % CB;
                 const bool is_out = t < n_out;
                 const int kt = is_out ? t : t - n_out;
-#ifdef ZEST_DW_EXP_NO_STAGE            // timing experiment only: the tiles never enter LDS (their loads become dead code)
-                if (b == b0)
-#endif
                 *reinterpret_cast<uint4 *>((is_out ? im_out : im_in) + (32 * sb + 16 * cb + col) * kImgStride + kt * 64 + grp * 16) =
                     pre[0][sb][i];
             }
         }
-#ifndef ZEST_DW_EXP_NO_SYNC             // (defined: timing experiment only, results are wrong)
         __syncthreads();
-#endif
 #pragma unroll
         for (int sb = 0; sb < NB; sb++) {
 #pragma unroll
@@ -140,11 +127,7 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_dw_kernel(
                 if (wave + 8 * i < items) pre[kDwAhead - 1][sb][i] = fetch_or_zero(b + (long long)kDwAhead * NB + sb, wave + 8 * i);
             }
         }
-#ifdef ZEST_DW_EXP_NO_MFMA             // timing experiment only
-        if (b == b0 && wave < n_out) {
-#else
         if (wave < n_out) {
-#endif
 #pragma unroll
             for (int sb = 0; sb < NB; sb++) {
                 const unsigned a_out = img0 + (unsigned)(buf * 2) * (NB * kImgBytes) + (unsigned)sb * kImgBytes;
@@ -183,9 +166,6 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void train16_dw_kernel(
     // the totals into the fp32 gradients.  (Float atomics from all 256 workgroups straight into the gradients -
     // 16.8 M of them - cost 88 of this kernel's 425 us.)
     float4 *mine = partial + ((size_t)blockIdx.x * kWaves + wave) * kDwSlots * 64 + lane;
-#ifdef ZEST_DW_EXP_NO_ATOMICS          // timing experiment only: results are wrong
-    if (acc[0][0][0] != 123456.0f) return;
-#endif
 #pragma unroll
     for (int rt = 0; rt < 2; rt++) {
 #pragma unroll

@@ -29,6 +29,7 @@ void zest_set_error(const char *fmt, ...);
     } while (0)
 
 static inline int zest_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- wave-level primitives (64 lanes) ---------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -24,9 +24,6 @@ __device__ __forceinline__ float zest_unnorm(float c01, int size) {
 __device__ __forceinline__ size_t zest_vox(int zi, int yi, int xi, int D, int W) {
     return ((size_t)yi * W + xi) * D + zi;
 }
-#ifdef ZEST_VOX_PLANES
-#error "the plane-major [D][H][W][8] copy of rounds 1-2 is gone; profiles/r03_ab_volume_layout.txt holds the A/B"
-#endif
 
 // Trilinear, zero padding.  vol: [H,W,D,8] (zest_vox) as float4 pairs.  CH4 selects which
 // half of the 8 channels (0: ch0-3, 1: ch4-7, 2: all eight -> out[0..7]).
@@ -81,7 +78,6 @@ __device__ __forceinline__ void zest_volume_trilerp(const float4 *__restrict__ v
 
 // One source view: world point -> pixel -> bilinear rgb (border clamp) + strict in-frame mask.
 // img: [H,W,4] of this view.  out = (r, g, b, mask).
-template <bool SAME_PIXEL = false>   // SAME_PIXEL: timing experiments only (all four taps read pixel 0)
 __device__ __forceinline__ float4 zest_color_tap(const float4 *__restrict__ img, int H, int W,
                                                  const ZestCam &c, float px, float py, float pz) {
     // p_cam = R p + T, q = K p_cam (reference utils.py:262-268), fp32, left-to-right sums
@@ -101,9 +97,8 @@ __device__ __forceinline__ float4 zest_color_tap(const float4 *__restrict__ img,
     const float tx = fx - x0f, ty = fy - y0f;
     const int x0 = (int)x0f, y0 = (int)y0f;
     const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-    const size_t keep = SAME_PIXEL ? 0 : ~(size_t)0;
-    const float4 a = img[((size_t)y0 * W + x0) & keep], b = img[((size_t)y0 * W + x1) & keep];
-    const float4 d = img[((size_t)y1 * W + x0) & keep], e = img[((size_t)y1 * W + x1) & keep];
+    const float4 a = img[(size_t)y0 * W + x0], b = img[(size_t)y0 * W + x1];
+    const float4 d = img[(size_t)y1 * W + x0], e = img[(size_t)y1 * W + x1];
     const float w00 = (1.0f - tx) * (1.0f - ty), w10 = tx * (1.0f - ty);
     const float w01 = (1.0f - tx) * ty, w11 = tx * ty;
     float4 o;

@@ -269,6 +269,44 @@ int zest_sf_reg_fwd(const float *ref, const float *post, const float *prev, cons
                     float scale_st, float w_sp, float w_st, float *loss_ray, float *d_ref, float *d_post,
                     float *d_prev, float *d_pp, void *stream);
 
+/* Per-sample terms of the scene-flow training loss (reference train.py:346-585), two launches.
+ * sf_*: [R,S,3] scene flows; prob_*, weights (weights_ref_dy), blend (raw_blend_w): [R,S]; all
+ * contiguous; a tensor no requested term reads may be NULL.
+ *   ZEST_SFS_CYCLE     mse_masked(sf_ref2post, -sf_post2ref, 1 - prob_ref2post) + the same for prev
+ *                      (train.py:450-457, losses.py:89-101; the mask and num_pix carry a gradient)
+ *   ZEST_SFS_PROB_REG  mean |prob_ref2prev| + mean |prob_ref2post|                (train.py:432-433)
+ *   ZEST_SFS_SF_MIN    mean_{r,s} |w_s sum_c sf_ref2prev| + the same of sf_ref2post (train.py:469-471:
+ *                      the reference's sum runs over the three components, not over the samples)
+ *   ZEST_SFS_ENTROPY   mean -blend log(blend + 1e-8)                              (train.py:520)
+ * zest_sf_sample_fwd writes partials [R, ZEST_SF_SAMPLE_COLS], one row per ray (m = 1 - prob):
+ *   0 sum_{s,c} m (a+b)^2 and 1 sum_s m of the post pair, 2, 3 of the prev pair; 4 sum |prob_ref2post|,
+ *   5 sum |prob_ref2prev|; 6 sum_s |w_s sum_c sf_ref2post|, 7 the same of sf_ref2prev;
+ *   8 sum -blend log(blend + 1e-8).  Columns of terms not requested are 0.  The caller sums the rows
+ * over the rays and forms the means; num_pix = 3 sum m + 1e-8.
+ * zest_sf_sample_bwd takes `totals` [ZEST_SF_SAMPLE_COLS], the column sums of partials, in device
+ * memory (columns 0..3 are read: no host synchronisation between the two launches), and
+ * writes d (c_cyc cycle + c_prob prob_reg + c_min sf_min + c_ent entropy) / d tensor into every
+ * d_* that is not NULL, in full (zeros where no requested term reads the tensor).
+ * Errors: R < 1, S < 1, an empty or unknown term mask, a NULL tensor that a requested term reads. */
+enum {
+    ZEST_SFS_CYCLE = 1,
+    ZEST_SFS_PROB_REG = 2,
+    ZEST_SFS_SF_MIN = 4,
+    ZEST_SFS_ENTROPY = 8
+};
+#define ZEST_SF_SAMPLE_COLS 9
+int zest_sf_sample_fwd(const float *sf_ref2post, const float *sf_post2ref, const float *sf_ref2prev,
+                       const float *sf_prev2ref, const float *prob_ref2post, const float *prob_ref2prev,
+                       const float *weights, const float *blend, int terms, int R, int S, float *partials,
+                       void *stream);
+int zest_sf_sample_bwd(const float *sf_ref2post, const float *sf_post2ref, const float *sf_ref2prev,
+                       const float *sf_prev2ref, const float *prob_ref2post, const float *prob_ref2prev,
+                       const float *weights, const float *blend, int terms, int R, int S,
+                       const float *totals, float c_cyc, float c_prob, float c_min, float c_ent,
+                       float *d_sf_ref2post, float *d_sf_post2ref, float *d_sf_ref2prev,
+                       float *d_sf_prev2ref, float *d_prob_ref2post, float *d_prob_ref2prev, float *d_weights,
+                       float *d_blend, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

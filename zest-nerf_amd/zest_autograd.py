@@ -351,6 +351,40 @@ class SceneFlowRegFn(Function):
         return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 6
 
 
+class SceneFlowSampleFn(Function):
+    """Per-sample terms of the scene-flow training loss (csrc/sf_sample_losses.hip).  The eight tensors of
+    zest_hip.SF_SAMPLE_TENSORS, contiguous fp32 [R,S,3] / [R,S] (None where no requested term reads one) ->
+    (total = c_cyc cycle + c_prob prob_reg + c_min sf_min + c_ent entropy, cycle, prob_reg, sf_min, entropy); only
+    `total` carries the graph.  When an input requires a gradient both launches happen here (the second reads the
+    reduced totals from device memory: no host synchronisation between them) and backward is the product with the
+    upstream scalar; otherwise only the forward launch runs."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        tensors, terms, coeff = list(args[:8]), args[8], args[9:13]
+        want = tuple(ctx.needs_input_grad[:8])
+        first = next(t for t in tensors if t is not None)
+        R, S = first.shape[0], first.shape[1]
+        partials = zest_hip.sf_sample_fwd(tensors, terms)
+        totals = partials.sum(0)
+        cycle = (totals[0:4:2] / (3.0 * totals[1:4:2] + 1e-8)).sum()      # num_pix = 3 sum m + 1e-8; 0 / 1e-8 if not requested
+        prob_reg = totals[4:6].sum() / float(R * S)
+        sf_min = totals[6:8].sum() / float(R * S)
+        entropy = totals[8] / float(R * S)
+        ctx.want = want
+        if any(want):
+            grads = zest_hip.sf_sample_bwd(tensors, totals, terms, coeff, want=want)
+            ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(cycle, prob_reg, sf_min, entropy)
+        total = coeff[0] * cycle + coeff[1] * prob_reg + coeff[2] * sf_min + coeff[3] * entropy
+        return total, cycle, prob_reg, sf_min, entropy
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        saved = iter(ctx.saved_tensors)
+        return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 5
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

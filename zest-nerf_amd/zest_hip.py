@@ -81,6 +81,8 @@ _SIGS = {
     "zest_project_rays_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, _vp]),
     "zest_project_rays_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _i, _i, _vp, _vp, _vp]),
     "zest_sf_reg_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zest_sf_sample_fwd": (_i, [_vp] * 8 + [_i, _i, _i, _vp, _vp]),
+    "zest_sf_sample_bwd": (_i, [_vp] * 8 + [_i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 8 + [_vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -347,6 +349,81 @@ def sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp=1.0, w_st=1.0, want=(Tr
                                  _ptr(loss_ray), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
                                  _stream(ref)), "zest_sf_reg_fwd")
     return loss_ray, out
+
+
+SFS_CYCLE, SFS_PROB_REG, SFS_SF_MIN, SFS_ENTROPY = 1, 2, 4, 8
+SFS_ALL = SFS_CYCLE | SFS_PROB_REG | SFS_SF_MIN | SFS_ENTROPY
+SF_SAMPLE_COLS = 9
+# the tensors of the per-sample terms, in the order of the C ABI, their trailing extent (0: none) and the terms that read them
+SF_SAMPLE_TENSORS = (("sf_ref2post", 3, SFS_CYCLE | SFS_SF_MIN), ("sf_post2ref", 3, SFS_CYCLE),
+                     ("sf_ref2prev", 3, SFS_CYCLE | SFS_SF_MIN), ("sf_prev2ref", 3, SFS_CYCLE),
+                     ("prob_ref2post", 0, SFS_CYCLE | SFS_PROB_REG), ("prob_ref2prev", 0, SFS_CYCLE | SFS_PROB_REG),
+                     ("weights", 0, SFS_SF_MIN), ("blend", 0, SFS_ENTROPY))
+
+
+def _sf_sample_inputs(who, tensors, terms):
+    """Shape, dtype, device and contiguity of the eight tensors (None where no requested term reads one), checked
+    before the library is touched -> (the tensors as given, R, S, terms)."""
+    terms = int(terms)
+    if len(tensors) != len(SF_SAMPLE_TENSORS):
+        raise RuntimeError("zest_hip: %s takes %d tensors, got %d" % (who, len(SF_SAMPLE_TENSORS), len(tensors)))
+    if terms <= 0 or terms & ~SFS_ALL:
+        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
+    for t, (name, _, readers) in zip(tensors, SF_SAMPLE_TENSORS):
+        if t is None and terms & readers:
+            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
+    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
+    if first.dim() < 2:
+        raise RuntimeError("zest_hip: %s needs tensors [R,S] and [R,S,3], got %s" % (who, tuple(first.shape)))
+    R, S = int(first.shape[0]), int(first.shape[1])
+    if R < 1 or S < 1:
+        raise RuntimeError("zest_hip: %s needs R >= 1 and S >= 1, got R=%d S=%d" % (who, R, S))
+    for t, (name, last, _) in zip(tensors, SF_SAMPLE_TENSORS):
+        if t is None:
+            continue
+        want = (R, S, 3) if last else (R, S)
+        if not t.is_cuda:
+            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
+                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
+    return R, S, terms
+
+
+def sf_sample_fwd(tensors, terms=SFS_ALL):
+    """Per-sample terms of the scene-flow training loss, forward launch.  tensors: the eight of SF_SAMPLE_TENSORS,
+    contiguous fp32 [R,S,3] / [R,S] (None where no requested term reads one) -> partials [R, SF_SAMPLE_COLS], one row
+    of partial sums per ray (include/zest_render.h names the columns)."""
+    R, S, terms = _sf_sample_inputs("sf_sample_fwd", tensors, terms)
+    first = next(t for t in tensors if t is not None)
+    partials = torch.empty(R, SF_SAMPLE_COLS, device=first.device, dtype=torch.float32)
+    _check(lib().zest_sf_sample_fwd(*[_ptr(t) for t in tensors], terms, R, S, _ptr(partials), _stream(first)),
+           "zest_sf_sample_fwd")
+    return partials
+
+
+def sf_sample_bwd(tensors, totals, terms=SFS_ALL, coeff=(1.0, 1.0, 1.0, 1.0), want=(True,) * 8, grads=None):
+    """Backward launch: totals [SF_SAMPLE_COLS] = sf_sample_fwd(...).sum(0) (it stays on the device), coeff = (c_cyc, c_prob, c_min, c_ent) -> the gradients of c_cyc cycle + c_prob prob_reg +
+    c_min sf_min + c_ent entropy with respect to the eight tensors (None where `want` is false or the tensor is None).
+    grads: optional preallocated tensors (or None) to write into; every row of them is written."""
+    R, S, terms = _sf_sample_inputs("sf_sample_bwd", tensors, terms)
+    first = next(t for t in tensors if t is not None)
+    if not torch.is_tensor(totals) or tuple(totals.shape) != (SF_SAMPLE_COLS,) or totals.dtype != torch.float32 \
+            or not totals.is_contiguous() or totals.device != first.device:
+        raise RuntimeError("zest_hip: sf_sample_bwd: totals must be a contiguous fp32 (%d,) on %s" % (SF_SAMPLE_COLS, first.device))
+    out = []
+    for k, t in enumerate(tensors):
+        g = None
+        if want[k] and t is not None:
+            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
+            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
+                raise RuntimeError("zest_hip: sf_sample_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
+                                   % (k, tuple(t.shape), first.device))
+        out.append(g)
+    c = [float(v) for v in coeff]
+    _check(lib().zest_sf_sample_bwd(*[_ptr(t) for t in tensors], terms, R, S, _ptr(totals), *c,
+                                    *[_ptr(g) for g in out], _stream(first)), "zest_sf_sample_bwd")
+    return out
 
 
 def nchw_to_nhwc(x):

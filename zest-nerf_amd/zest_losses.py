@@ -8,15 +8,24 @@ instead of building [N,R,S,S] tensors.
 (losses.py:142-203); `scene_flow_regularisers` evaluates the whole set the training step evaluates
 (train.py:480-510: two spatial and two temporal terms) in ONE launch of csrc/sf_losses.hip, which
 also yields the gradients with respect to the four point tensors.  Where the reference returns NaN
-(an empty batch, rays too short for a difference) these raise.  The other names of the reference's
-losses.py are image-space terms outside this path.
+(an empty batch, rays too short for a difference) these raise.
+
+`scene_flow_sample_terms` evaluates the other terms of the training step that walk per-sample outputs of
+rendering() - flow cycle consistency, the disocclusion-weight regulariser, minimal scene flow and the
+blending entropy (train.py:432-433, 450-457, 469-471, 520) - in two launches of csrc/sf_sample_losses.hip,
+values and gradients.  `train_sf_step_loss` is the whole loss of a scene-flow training step (the reference's
+MVSNeRFSystem.train_sf_step, train.py:346-585) on top of these pieces and `zest_utils.projection_from_ndc`;
+its per-ray terms (masked photometric errors, flow error, whitened depth prior: [R,3] tensors) are torch.
+The other names of the reference's losses.py are image-space terms outside this path.
 """
 import torch
 
 import zest_autograd
 import zest_hip
+import zest_utils
 
-__all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers"]
+__all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers",
+           "scene_flow_sample_terms", "train_sf_step_loss"]
 
 
 def distortion_loss(ray_weights, t_vals):
@@ -92,3 +101,134 @@ def scene_flow_regularisers(raw_pts_ref, raw_pts_post, raw_pts_prev, raw_pts_pp,
     else:
         terms |= zest_hip.SF_LKE_CHAIN_BWD if chain_bwd else zest_hip.SF_LKE_CHAIN_FWD
     return zest_autograd.SceneFlowRegFn.apply(*pts, terms, H, W, f, float(w_sp), float(w_st))
+
+
+def _sf_samples(who, named):
+    """Check the eight tensors of the per-sample terms BEFORE the library is touched and flatten them to contiguous
+    fp32 [R,S,3] / [R,S].  named: [(argument name, tensor, trailing extent or 0)]; the leading dimensions and S agree."""
+    first_name, first, _ = named[0]
+    for name, t, last in named:
+        if not torch.is_tensor(t) or t.dim() < (3 if last else 2) or (last and t.shape[-1] != last):
+            raise RuntimeError("%s: %s must be a tensor [..., N_samples%s], got %s"
+                               % (who, name, ", 3" if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        lead = t.shape[:-1] if last else t.shape
+        if lead != first.shape[:-1]:
+            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
+    if first.numel() == 0:
+        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
+    for name, t, _ in named:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if t.device != first.device:
+            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
+    S = first.shape[-2]
+    return [t.contiguous().float().reshape(-1, S, 3) if last else t.contiguous().float().reshape(-1, S) for _, t, last in named]
+
+
+def scene_flow_sample_terms(raw_sf_ref2post, raw_sf_post2ref, raw_sf_ref2prev, raw_sf_prev2ref, raw_prob_ref2post,
+                            raw_prob_ref2prev, weights_ref_dy, raw_blend_w, w_cyc=1.0, w_prob=1.0, w_min=1.0, w_entropy=1.0):
+    """The per-sample terms of one scene-flow training step, values and gradients from two launches:
+        sf_cycle_loss = mse_masked(sf_ref2post, -sf_post2ref, 1 - prob_ref2post) + the same for prev   (train.py:450-457)
+        prob_reg_loss = mean |prob_ref2prev| + mean |prob_ref2post|                                    (train.py:432-433)
+        sf_min_loss   = mean |w sum_c sf_ref2prev| + mean |w sum_c sf_ref2post|, over rays and samples (train.py:469-471)
+        entropy_loss  = mean -blend log(blend + 1e-8)                                                  (train.py:520)
+    raw_sf_*: [..., N_samples, 3]; the others [..., N_samples] ->
+    (w_cyc cycle + w_prob prob_reg + w_min sf_min + w_entropy entropy, with the graph; the four values, detached)."""
+    named = [("raw_sf_ref2post", raw_sf_ref2post, 3), ("raw_sf_post2ref", raw_sf_post2ref, 3),
+             ("raw_sf_ref2prev", raw_sf_ref2prev, 3), ("raw_sf_prev2ref", raw_sf_prev2ref, 3),
+             ("raw_prob_ref2post", raw_prob_ref2post, 0), ("raw_prob_ref2prev", raw_prob_ref2prev, 0),
+             ("weights_ref_dy", weights_ref_dy, 0), ("raw_blend_w", raw_blend_w, 0)]
+    flat = _sf_samples("scene_flow_sample_terms", named)
+    return zest_autograd.SceneFlowSampleFn.apply(*flat, zest_hip.SFS_ALL, float(w_cyc), float(w_prob), float(w_min),
+                                                 float(w_entropy))
+
+
+def _masked_mean(err, mask):
+    """sum(err * mask) / (sum(mask over err's last extent) + 1e-8): mse_masked / mae_masked (losses.py:89-116).  The
+    mask [..., 1] carries a gradient, also through the denominator."""
+    m = mask.expand_as(err)
+    return (err * m).sum() / (m.sum() + 1e-8)
+
+
+def _whitened_depth_loss(pred, gt):
+    """compute_depth_loss (losses.py:118-140): both maps shifted by their median and scaled by their mean absolute
+    deviation, mean squared difference."""
+    def whiten(d):
+        t = torch.median(d)
+        return (d - t) / (d - t).abs().mean()
+    return ((whiten(pred) - whiten(gt)) ** 2).mean()
+
+
+def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_frames, hparams, global_step,
+                       decay_iteration, loss=None):
+    """The loss of one scene-flow training step: MVSNeRFSystem.train_sf_step (train.py:346-585) without its class.
+    results: what rendering() returned plus the ground truth the step reads (the reference's keys); images_shape:
+    batch['images'].shape, [N,V,C,H,W]; focal: batch['intrinsics'][:,-1,0,0]; fnb_w2cs [1,2,4,4]: world-to-camera of
+    the previous and the next frame; hparams: the lambda_* coefficients (attributes or keys); decay_iteration: the
+    system's (min(hparams.decay_iteration, 250) in the reference); loss: the image criterion (default nn.MSELoss()).
+    -> (sceneflow_loss with the graph, {name: logged value}) with the reference's ten names, weighted as it logs them."""
+    if isinstance(hparams, dict):
+        hp = hparams.__getitem__
+    else:
+        def hp(name):
+            return getattr(hparams, name)
+    if loss is None:
+        loss = torch.nn.MSELoss(reduction="mean")
+    r = results
+    H, W = int(images_shape[-2]), int(images_shape[-1])
+    focal = float(focal)
+    rgb_gt = r["target_s"]
+    chain_bwd, chain_5frames = bool(r["chain_bwd"]), bool(r["chain_5frames"])
+    logs = {}
+
+    # temporal photometric consistency of the dynamic-only renders
+    dd = r["weights_map_dd"].unsqueeze(-1).detach()
+    p_post, p_prev = r["prob_map_post"].unsqueeze(-1), r["prob_map_prev"].unsqueeze(-1)
+    if global_step <= decay_iteration * 1000:               # initialisation phase
+        pho = loss(r["rgb_map_ref_dy"], rgb_gt)
+        pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post)
+        pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev)
+    else:
+        pho = _masked_mean((r["rgb_map_ref_dy"] - rgb_gt) ** 2, dd)
+        pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post * dd)
+        pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev * dd)
+    if chain_5frames:
+        pho = pho + _masked_mean((r["rgb_map_pp_dy"] - rgb_gt) ** 2, dd)
+    logs["pho_loss"] = pho.detach()
+    combined = loss(r["rgb_map_ref"], rgb_gt)
+    logs["combined_loss"] = combined.detach()
+
+    # the per-sample terms: one pair of launches
+    l_cyc, l_prob, l_min, l_ent = (hp("lambda_cyc"), hp("lambda_prob_reg"), hp("lambda_sf_reg"), hp("lambda_blending_reg"))
+    samples, cyc, prob_reg, sf_min, entropy = scene_flow_sample_terms(
+        r["raw_sf_ref2post"], r["raw_sf_post2ref"], r["raw_sf_ref2prev"], r["raw_sf_prev2ref"], r["raw_prob_ref2post"],
+        r["raw_prob_ref2prev"], r["weights_ref_dy"], r["raw_blend_w"], w_cyc=l_cyc, w_prob=l_prob, w_min=l_min, w_entropy=l_ent)
+    logs["prob_reg_loss"], logs["sf_cycle_loss"] = l_prob * prob_reg, l_cyc * cyc
+    logs["sf_min_loss"], logs["entropy_loss"] = l_min * sf_min, l_ent * entropy
+
+    # spatial and temporal smoothness of the flow: one launch
+    l_smooth = hp("lambda_sf_smooth")
+    regs, sf_sp, sf_st = scene_flow_regularisers(r["raw_pts_ref"], r["raw_pts_post"], r["raw_pts_prev"], r["raw_pts_pp"],
+                                                 chain_bwd, H, W, focal, w_sp=l_smooth, w_st=l_smooth)
+    logs["sf_sp_loss"], logs["sf_st_loss"] = l_smooth * sf_sp, l_smooth * sf_st
+
+    # data-driven priors, decayed by 10 every decay_iteration * 1000 steps
+    divisor = global_step // (decay_iteration * 1000)
+    w_of = hp("lambda_optical_flow") / (10 ** divisor)
+    w_depth = hp("lambda_sf_depth") / (10 ** divisor)
+
+    def flow_error(k, pts, gt, mask):                        # k: 1 the next frame, 0 the previous
+        render = zest_utils.projection_from_ndc(fnb_w2cs[:, k], H, W, focal, r["weights_ref_dy"], r[pts])
+        return _masked_mean((render - r[gt]).abs(), r[mask].unsqueeze(-1))
+    if frame_t == 0:                                         # the first frame has forward flow only
+        flow = flow_error(1, "raw_pts_post", "rays_flow_fwd_gt", "rays_mask_fwd_gt")
+    elif frame_t == total_frames - 1:                        # the last, backward only
+        flow = flow_error(0, "raw_pts_prev", "rays_flow_bwd_gt", "rays_mask_bwd_gt")
+    else:
+        flow = flow_error(1, "raw_pts_post", "rays_flow_fwd_gt", "rays_mask_fwd_gt") \
+            + flow_error(0, "raw_pts_prev", "rays_flow_bwd_gt", "rays_mask_bwd_gt")
+    logs["flow_loss"] = (w_of * flow).detach()
+    depth = _whitened_depth_loss(r["depth_map_ref_dy"], -r["depth_gt"])
+    logs["sf_depth_loss"] = (w_depth * depth).detach()
+
+    return pho + combined + samples + regs + w_of * flow + w_depth * depth, logs

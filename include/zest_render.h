@@ -307,6 +307,64 @@ int zest_sf_sample_bwd(const float *sf_ref2post, const float *sf_post2ref, const
                        float *d_sf_prev2ref, float *d_prob_ref2post, float *d_prob_ref2prev, float *d_weights,
                        float *d_blend, void *stream);
 
+/* Per-ray terms of the scene-flow training loss (reference train.py:395-430, 512-575,
+ * losses.py:89-140), one launch forward (a single workgroup of ZEST_SF_RAY_FWD_THREADS that strides
+ * over the rays: any R >= 1), one launch backward (ZEST_SF_RAY_BWD_THREADS rays per workgroup).
+ * target (target_s), rgb_*: [R,3]; prob_post, prob_prev (prob_map_*), weights_dd (weights_map_dd),
+ * mask_*, depth (depth_map_ref_dy), depth_gt: [R]; flow_* (the output of zest_project_rays_fwd) and
+ * flow_*_gt: [R,2]; all contiguous; a tensor no requested term reads may be NULL.
+ *   ZEST_SFR_PHO       sum over the maps j = ref_dy, post_dy, prev_dy (and pp_dy if five_frames) of
+ *                      N_j / (3 M_j + 1e-8), N_j = sum_{r,c} m_j (rgb_j - target)^2, M_j = sum_r m_j, with the
+ *                      masks m = (1, prob_post, prob_prev, dd) and, if late_phase, (dd, prob_post dd,
+ *                      prob_prev dd, dd); the unmasked map is the plain mean N / (3 R).  prob_post and
+ *                      prob_prev carry a gradient, also through M; weights_dd carries none.  weights_dd
+ *                      is read if late_phase or five_frames, rgb_pp_dy if five_frames.
+ *   ZEST_SFR_COMBINED  mean (rgb_ref - target)^2
+ *   ZEST_SFR_FLOW_FWD  sum |flow_fwd - flow_fwd_gt| mask_fwd / (2 sum mask_fwd + 1e-8); _BWD the same
+ *   ZEST_SFR_DEPTH     mean (whiten(depth) - whiten(-depth_gt))^2, whiten(d) = (d - med d) / mean |d - med d|,
+ *                      med the element of rank (R - 1) / 2, as torch.median.  R = 1 gives 0 / 0.
+ * zest_sf_ray_fwd writes result [ZEST_SF_RAY_COLS]: 0 pho, 1 combined, 2 flow (the sum of the
+ *   requested directions), 3 depth, 0 where not requested; 4..11 (N_j, M_j) of the four maps; 12 the sum
+ *   of the combined term; 13..16 (sum |d| mask, sum mask) forward, backward; 17, 18 median and scale
+ *   of depth, 19, 20 of -depth_gt; 21 sum (wa - wb), 22 sum (wa - wb) wa over the whitened maps,
+ *   23 sum sign(depth - median); 24 the index of the median element of depth, an int32 bit pattern;
+ *   25 c_pho pho + c_comb combined + c_flow flow + c_depth depth.
+ * zest_sf_ray_bwd takes that row as `totals`, in device memory (no host synchronisation between
+ *   the two launches), and writes d (c_pho pho + c_comb combined + c_flow flow + c_depth depth) /
+ *   d tensor into every d_* that is not NULL, in full (zeros where no requested term reads the tensor).
+ *   The depth gradient includes the paths through the scale and through the median element; where
+ *   several rays hold the median value, the median's share goes to exactly one of them, the first.
+ *   |0| has gradient 0.
+ * No atomics on floats: two calls on the same inputs are bit-identical.
+ * Errors: R < 1, an empty or unknown term mask, a NULL tensor that a requested term reads, a NULL
+ * result, NULL totals. */
+enum {
+    ZEST_SFR_PHO = 1,
+    ZEST_SFR_COMBINED = 2,
+    ZEST_SFR_FLOW_FWD = 4,
+    ZEST_SFR_FLOW_BWD = 8,
+    ZEST_SFR_DEPTH = 16
+};
+#define ZEST_SF_RAY_COLS 26
+#define ZEST_SF_RAY_FWD_THREADS 1024
+#define ZEST_SF_RAY_BWD_THREADS 256
+int zest_sf_ray_fwd(const float *target, const float *rgb_ref, const float *rgb_ref_dy, const float *rgb_post_dy,
+                    const float *rgb_prev_dy, const float *rgb_pp_dy, const float *prob_post,
+                    const float *prob_prev, const float *weights_dd, const float *flow_fwd,
+                    const float *flow_fwd_gt, const float *mask_fwd, const float *flow_bwd,
+                    const float *flow_bwd_gt, const float *mask_bwd, const float *depth, const float *depth_gt,
+                    int terms, int late_phase, int five_frames, int R, float c_pho, float c_comb, float c_flow,
+                    float c_depth, float *result, void *stream);
+int zest_sf_ray_bwd(const float *target, const float *rgb_ref, const float *rgb_ref_dy, const float *rgb_post_dy,
+                    const float *rgb_prev_dy, const float *rgb_pp_dy, const float *prob_post,
+                    const float *prob_prev, const float *weights_dd, const float *flow_fwd,
+                    const float *flow_fwd_gt, const float *mask_fwd, const float *flow_bwd,
+                    const float *flow_bwd_gt, const float *mask_bwd, const float *depth, const float *depth_gt,
+                    int terms, int late_phase, int five_frames, int R, const float *totals, float c_pho,
+                    float c_comb, float c_flow, float c_depth, float *d_rgb_ref, float *d_rgb_ref_dy,
+                    float *d_rgb_post_dy, float *d_rgb_prev_dy, float *d_rgb_pp_dy, float *d_prob_post,
+                    float *d_prob_prev, float *d_flow_fwd, float *d_flow_bwd, float *d_depth, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

@@ -385,6 +385,37 @@ class SceneFlowSampleFn(Function):
         return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 5
 
 
+class SceneFlowRayFn(Function):
+    """Per-ray terms of the scene-flow training loss (csrc/sf_ray_losses.hip).  The seventeen tensors of
+    zest_hip.SF_RAY_TENSORS, contiguous fp32 [R,3] / [R,2] / [R] (None where no requested term reads one), then terms,
+    late_phase, five_frames, the coefficients (c_pho, c_comb, c_flow, c_depth) and the caller's torch.is_grad_enabled()
+    (forward itself always runs with the graph switched off, and needs_input_grad does not know about no_grad) ->
+    (total = c_pho pho + c_comb combined + c_flow flow + c_depth depth, pho, combined, flow, depth); only `total`
+    carries the graph.  When an input requires a gradient and the graph is recorded both launches happen here (the second reads the first's
+    result row from device memory: no host synchronisation between them) and backward is the product with the
+    upstream scalar; otherwise only the forward launch runs."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        n = len(zest_hip.SF_RAY_TENSORS)
+        tensors, (terms, late_phase, five_frames), coeff, recording = list(args[:n]), args[n:n + 3], args[n + 3:n + 7], args[n + 7]
+        want = tuple(bool(recording) and ctx.needs_input_grad[i] for i in zest_hip.SF_RAY_GRADS)
+        result = zest_hip.sf_ray_fwd(tensors, terms, late_phase, five_frames, coeff)
+        pho, combined, flow, depth, total = result[0], result[1], result[2], result[3], result[zest_hip.SF_RAY_COLS - 1]
+        ctx.want = want
+        if any(want):
+            grads = zest_hip.sf_ray_bwd(tensors, result, terms, late_phase, five_frames, coeff, want=want)
+            ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(pho, combined, flow, depth)
+        return total, pho, combined, flow, depth
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        saved = iter(ctx.saved_tensors)
+        by_pos = dict(zip(zest_hip.SF_RAY_GRADS, (next(saved) * g if w else None for w in ctx.want)))
+        return tuple(by_pos.get(i) for i in range(len(zest_hip.SF_RAY_TENSORS))) + (None,) * 8
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

@@ -83,6 +83,8 @@ _SIGS = {
     "zest_sf_reg_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zest_sf_sample_fwd": (_i, [_vp] * 8 + [_i, _i, _i, _vp, _vp]),
     "zest_sf_sample_bwd": (_i, [_vp] * 8 + [_i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 8 + [_vp]),
+    "zest_sf_ray_fwd": (_i, [_vp] * 17 + [_i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp]),
+    "zest_sf_ray_bwd": (_i, [_vp] * 17 + [_i, _i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 10 + [_vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -423,6 +425,88 @@ def sf_sample_bwd(tensors, totals, terms=SFS_ALL, coeff=(1.0, 1.0, 1.0, 1.0), wa
     c = [float(v) for v in coeff]
     _check(lib().zest_sf_sample_bwd(*[_ptr(t) for t in tensors], terms, R, S, _ptr(totals), *c,
                                     *[_ptr(g) for g in out], _stream(first)), "zest_sf_sample_bwd")
+    return out
+
+
+SFR_PHO, SFR_COMBINED, SFR_FLOW_FWD, SFR_FLOW_BWD, SFR_DEPTH = 1, 2, 4, 8, 16
+SFR_ALL = SFR_PHO | SFR_COMBINED | SFR_FLOW_FWD | SFR_FLOW_BWD | SFR_DEPTH
+SF_RAY_COLS = 26
+SF_RAY_FWD_THREADS, SF_RAY_BWD_THREADS = 1024, 256       # the forward's only workgroup; rays per workgroup of the backward
+# the tensors of the per-ray terms, in the order of the C ABI: name, trailing extent (0: none), the terms that read it
+# (rgb_pp_dy only with five_frames, weights_dd only with late_phase or five_frames), whether it takes a gradient
+SF_RAY_TENSORS = (("target", 3, SFR_PHO | SFR_COMBINED, False), ("rgb_ref", 3, SFR_COMBINED, True),
+                  ("rgb_ref_dy", 3, SFR_PHO, True), ("rgb_post_dy", 3, SFR_PHO, True), ("rgb_prev_dy", 3, SFR_PHO, True),
+                  ("rgb_pp_dy", 3, SFR_PHO, True), ("prob_post", 0, SFR_PHO, True), ("prob_prev", 0, SFR_PHO, True),
+                  ("weights_dd", 0, SFR_PHO, False), ("flow_fwd", 2, SFR_FLOW_FWD, True), ("flow_fwd_gt", 2, SFR_FLOW_FWD, False),
+                  ("mask_fwd", 0, SFR_FLOW_FWD, False), ("flow_bwd", 2, SFR_FLOW_BWD, True), ("flow_bwd_gt", 2, SFR_FLOW_BWD, False),
+                  ("mask_bwd", 0, SFR_FLOW_BWD, False), ("depth", 0, SFR_DEPTH, True), ("depth_gt", 0, SFR_DEPTH, False))
+SF_RAY_GRADS = tuple(k for k, t in enumerate(SF_RAY_TENSORS) if t[3])        # positions of the ten that take a gradient
+
+
+def _sf_ray_inputs(who, tensors, terms, late_phase, five_frames):
+    """Shape, dtype, device and contiguity of the seventeen tensors (None where no requested term reads one), checked
+    before the library is touched -> (R, terms)."""
+    terms = int(terms)
+    if len(tensors) != len(SF_RAY_TENSORS):
+        raise RuntimeError("zest_hip: %s takes %d tensors, got %d" % (who, len(SF_RAY_TENSORS), len(tensors)))
+    if terms <= 0 or terms & ~SFR_ALL:
+        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
+    for t, (name, _, readers, _) in zip(tensors, SF_RAY_TENSORS):
+        read = terms & readers and (name != "rgb_pp_dy" or five_frames) and (name != "weights_dd" or late_phase or five_frames)
+        if t is None and read:
+            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
+    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
+    R = int(first.shape[0]) if first.dim() else 0
+    if R < 1:
+        raise RuntimeError("zest_hip: %s needs R >= 1, got %s" % (who, tuple(first.shape)))
+    for t, (name, last, _, _) in zip(tensors, SF_RAY_TENSORS):
+        if t is None:
+            continue
+        want = (R, last) if last else (R,)
+        if not t.is_cuda:
+            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
+                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
+    return R, terms
+
+
+def sf_ray_fwd(tensors, terms=SFR_ALL, late_phase=False, five_frames=True, coeff=(1.0, 1.0, 1.0, 1.0)):
+    """Per-ray terms of the scene-flow training loss, forward launch.  tensors: the seventeen of SF_RAY_TENSORS,
+    contiguous fp32 [R,3] / [R,2] / [R] (None where no requested term reads one) -> result [SF_RAY_COLS]: pho, combined,
+    flow, depth, then the sums, medians and scales the backward reads, last c_pho pho + c_comb combined + c_flow flow +
+    c_depth depth for coeff = (c_pho, c_comb, c_flow, c_depth) (include/zest_render.h names the columns)."""
+    R, terms = _sf_ray_inputs("sf_ray_fwd", tensors, terms, late_phase, five_frames)
+    first = next(t for t in tensors if t is not None)
+    result = torch.empty(SF_RAY_COLS, device=first.device, dtype=torch.float32)
+    _check(lib().zest_sf_ray_fwd(*[_ptr(t) for t in tensors], terms, int(bool(late_phase)), int(bool(five_frames)), R,
+                                 *[float(v) for v in coeff], _ptr(result), _stream(first)), "zest_sf_ray_fwd")
+    return result
+
+
+def sf_ray_bwd(tensors, totals, terms=SFR_ALL, late_phase=False, five_frames=True, coeff=(1.0, 1.0, 1.0, 1.0),
+               want=(True,) * 10, grads=None):
+    """Backward launch: totals [SF_RAY_COLS] = sf_ray_fwd(...) (it stays on the device), coeff = (c_pho, c_comb, c_flow,
+    c_depth) -> the gradients of c_pho pho + c_comb combined + c_flow flow + c_depth depth with respect to the ten
+    tensors of SF_RAY_GRADS, in that order (None where `want` is false or the tensor is None).  grads: optional
+    preallocated tensors (or None) to write into; every row of them is written."""
+    R, terms = _sf_ray_inputs("sf_ray_bwd", tensors, terms, late_phase, five_frames)
+    first = next(t for t in tensors if t is not None)
+    if not torch.is_tensor(totals) or tuple(totals.shape) != (SF_RAY_COLS,) or totals.dtype != torch.float32 \
+            or not totals.is_contiguous() or totals.device != first.device:
+        raise RuntimeError("zest_hip: sf_ray_bwd: totals must be a contiguous fp32 (%d,) on %s" % (SF_RAY_COLS, first.device))
+    out = []
+    for k, i in enumerate(SF_RAY_GRADS):
+        t, g = tensors[i], None
+        if want[k] and t is not None:
+            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
+            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
+                raise RuntimeError("zest_hip: sf_ray_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
+                                   % (k, tuple(t.shape), first.device))
+        out.append(g)
+    c = [float(v) for v in coeff]
+    _check(lib().zest_sf_ray_bwd(*[_ptr(t) for t in tensors], terms, int(bool(late_phase)), int(bool(five_frames)), R,
+                                 _ptr(totals), *c, *[_ptr(g) for g in out], _stream(first)), "zest_sf_ray_bwd")
     return out
 
 

@@ -14,8 +14,12 @@ also yields the gradients with respect to the four point tensors.  Where the ref
 rendering() - flow cycle consistency, the disocclusion-weight regulariser, minimal scene flow and the
 blending entropy (train.py:432-433, 450-457, 469-471, 520) - in two launches of csrc/sf_sample_losses.hip,
 values and gradients.  `train_sf_step_loss` is the whole loss of a scene-flow training step (the reference's
-MVSNeRFSystem.train_sf_step, train.py:346-585) on top of these pieces and `zest_utils.projection_from_ndc`;
-its per-ray terms (masked photometric errors, flow error, whitened depth prior: [R,3] tensors) are torch.
+MVSNeRFSystem.train_sf_step, train.py:346-585) on top of these pieces and `zest_utils.projection_from_ndc`.
+
+`scene_flow_ray_terms` evaluates the per-ray terms of that step - the masked photometric errors, the combined image
+error, the optical-flow error and the whitened depth prior with its two medians (train.py:395-430, 512-575,
+losses.py:89-140) - in two launches of csrc/sf_ray_losses.hip, values and gradients; `train_sf_step_loss` routes
+them there (`ray_terms="hip"`, the default) or through the torch composition it had before (`ray_terms="torch"`).
 The other names of the reference's losses.py are image-space terms outside this path.
 """
 import torch
@@ -25,7 +29,7 @@ import zest_hip
 import zest_utils
 
 __all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers",
-           "scene_flow_sample_terms", "train_sf_step_loss"]
+           "scene_flow_sample_terms", "scene_flow_ray_terms", "train_sf_step_loss"]
 
 
 def distortion_loss(ray_weights, t_vals):
@@ -143,6 +147,77 @@ def scene_flow_sample_terms(raw_sf_ref2post, raw_sf_post2ref, raw_sf_ref2prev, r
                                                  float(w_entropy))
 
 
+def _sf_rays(who, named, with_depth):
+    """Check the tensors of the per-ray terms BEFORE the library is touched and flatten them to contiguous fp32 [R,3] /
+    [R,2] / [R].  named: [(argument name, tensor or None, trailing extent or 0)]; the first is there and the leading
+    dimensions agree.  Shapes first, then the batch (empty; a single ray under the whitened depths), then the device."""
+    first_name, first, _ = named[0]
+    given = [(name, t, last) for name, t, last in named if t is not None]
+    for name, t, last in given:
+        if not torch.is_tensor(t) or t.dim() < (1 if last else 0) or (last and t.shape[-1] != last):
+            raise RuntimeError("%s: %s must be a tensor [...%s], got %s"
+                               % (who, name, ", %d" % last if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    lead = first.shape[:-1]
+    for name, t, last in given:
+        if (t.shape[:-1] if last else t.shape) != lead:
+            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
+    if first.numel() == 0:
+        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
+    if with_depth and first.numel() == first.shape[-1]:
+        raise RuntimeError("%s: one ray %s: its depth is its own median, the whitened depth prior is 0 / 0"
+                           % (who, tuple(first.shape)))
+    for name, t, _ in given:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if t.device != first.device:
+            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
+    return [None if t is None else t.contiguous().float().reshape(-1, last) if last else t.contiguous().float().reshape(-1)
+            for _, t, last in named]
+
+
+def scene_flow_ray_terms(target_s, rgb_map_ref, rgb_map_ref_dy, rgb_map_post_dy, rgb_map_prev_dy, rgb_map_pp_dy,
+                         prob_map_post, prob_map_prev, weights_map_dd, flow_fwd, rays_flow_fwd_gt, rays_mask_fwd_gt,
+                         flow_bwd, rays_flow_bwd_gt, rays_mask_bwd_gt, depth_map_ref_dy, depth_gt, late_phase,
+                         w_flow=1.0, w_depth=1.0):
+    """The per-ray terms of one scene-flow training step, values and gradients from two launches:
+        pho_loss      = mse(rgb_ref_dy) + mse_masked(rgb_post_dy, prob_post) + mse_masked(rgb_prev_dy, prob_prev), or, if
+                        late_phase, mse_masked with the masks dd, prob_post dd, prob_prev dd; + mse_masked(rgb_pp_dy, dd)
+                        where rgb_map_pp_dy is given (the five-frame chain); every error against target_s; the
+                        probabilities carry a gradient, also through num_pix, dd = weights_map_dd none (train.py:395-430)
+        combined_loss = mse(rgb_map_ref, target_s)                                                    (train.py:512)
+        flow_loss     = mae_masked(flow_fwd, rays_flow_fwd_gt, rays_mask_fwd_gt) + the same backward; flow_* are
+                        projection_from_ndc's outputs; one that is None (the first / last frame) is left out, with
+                        its ground truth and mask                                                      (train.py:535-563)
+        depth_loss    = compute_depth_loss(depth_map_ref_dy, -depth_gt): both whitened by their median and mean
+                        absolute deviation, mean squared difference; a constant map gives a non-finite value, as in
+                        the reference                                                        (train.py:565-575, losses.py:118-140)
+    target_s, rgb_*: [..., 3]; flow_*: [..., 2]; the others [...] ->
+    (pho + combined + w_flow flow + w_depth depth, with the graph; pho, combined, flow, depth, detached)."""
+    named = [("target_s", target_s, 3), ("rgb_map_ref", rgb_map_ref, 3), ("rgb_map_ref_dy", rgb_map_ref_dy, 3),
+             ("rgb_map_post_dy", rgb_map_post_dy, 3), ("rgb_map_prev_dy", rgb_map_prev_dy, 3),
+             ("rgb_map_pp_dy", rgb_map_pp_dy, 3), ("prob_map_post", prob_map_post, 0), ("prob_map_prev", prob_map_prev, 0),
+             ("weights_map_dd", weights_map_dd, 0),
+             ("flow_fwd", flow_fwd, 2), ("rays_flow_fwd_gt", None if flow_fwd is None else rays_flow_fwd_gt, 2),
+             ("rays_mask_fwd_gt", None if flow_fwd is None else rays_mask_fwd_gt, 0),
+             ("flow_bwd", flow_bwd, 2), ("rays_flow_bwd_gt", None if flow_bwd is None else rays_flow_bwd_gt, 2),
+             ("rays_mask_bwd_gt", None if flow_bwd is None else rays_mask_bwd_gt, 0),
+             ("depth_map_ref_dy", depth_map_ref_dy, 0), ("depth_gt", depth_gt, 0)]
+    who = "scene_flow_ray_terms"
+    for name, t, _ in named:
+        if t is None and name not in ("rgb_map_pp_dy", "flow_fwd", "rays_flow_fwd_gt", "rays_mask_fwd_gt", "flow_bwd",
+                                      "rays_flow_bwd_gt", "rays_mask_bwd_gt"):
+            raise RuntimeError("%s: %s is None (only rgb_map_pp_dy and the rendered flows may be)" % (who, name))
+    for flow, gt, mask in ((flow_fwd, rays_flow_fwd_gt, rays_mask_fwd_gt), (flow_bwd, rays_flow_bwd_gt, rays_mask_bwd_gt)):
+        if flow is not None and (gt is None or mask is None):
+            raise RuntimeError("%s: a rendered flow is given without its ground truth or its mask" % who)
+    flat = _sf_rays(who, named, True)
+    flat[8] = flat[8].detach()                                  # weights_map_dd carries no gradient (train.py:396)
+    terms = zest_hip.SFR_PHO | zest_hip.SFR_COMBINED | zest_hip.SFR_DEPTH
+    terms |= (zest_hip.SFR_FLOW_FWD if flow_fwd is not None else 0) | (zest_hip.SFR_FLOW_BWD if flow_bwd is not None else 0)
+    return zest_autograd.SceneFlowRayFn.apply(*flat, terms, bool(late_phase), rgb_map_pp_dy is not None, 1.0, 1.0,
+                                              float(w_flow), float(w_depth), torch.is_grad_enabled())
+
+
 def _masked_mean(err, mask):
     """sum(err * mask) / (sum(mask over err's last extent) + 1e-8): mse_masked / mae_masked (losses.py:89-116).  The
     mask [..., 1] carries a gradient, also through the denominator."""
@@ -160,20 +235,25 @@ def _whitened_depth_loss(pred, gt):
 
 
 def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_frames, hparams, global_step,
-                       decay_iteration, loss=None):
+                       decay_iteration, loss=None, ray_terms="hip"):
     """The loss of one scene-flow training step: MVSNeRFSystem.train_sf_step (train.py:346-585) without its class.
     results: what rendering() returned plus the ground truth the step reads (the reference's keys); images_shape:
     batch['images'].shape, [N,V,C,H,W]; focal: batch['intrinsics'][:,-1,0,0]; fnb_w2cs [1,2,4,4]: world-to-camera of
     the previous and the next frame; hparams: the lambda_* coefficients (attributes or keys); decay_iteration: the
-    system's (min(hparams.decay_iteration, 250) in the reference); loss: the image criterion (default nn.MSELoss()).
+    system's (min(hparams.decay_iteration, 250) in the reference); loss: the image criterion (default nn.MSELoss());
+    ray_terms: "hip" evaluates the per-ray terms in scene_flow_ray_terms, "torch" as a torch composition (so does any
+    `loss` that is not a mean-reduced nn.MSELoss: the kernel knows that criterion only).
     -> (sceneflow_loss with the graph, {name: logged value}) with the reference's ten names, weighted as it logs them."""
     if isinstance(hparams, dict):
         hp = hparams.__getitem__
     else:
         def hp(name):
             return getattr(hparams, name)
+    if ray_terms not in ("hip", "torch"):
+        raise RuntimeError("train_sf_step_loss: ray_terms must be 'hip' or 'torch', got %r" % (ray_terms,))
     if loss is None:
         loss = torch.nn.MSELoss(reduction="mean")
+    rays_hip = ray_terms == "hip" and type(loss) is torch.nn.MSELoss and loss.reduction == "mean"
     r = results
     H, W = int(images_shape[-2]), int(images_shape[-1])
     focal = float(focal)
@@ -182,21 +262,22 @@ def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_fr
     logs = {}
 
     # temporal photometric consistency of the dynamic-only renders
-    dd = r["weights_map_dd"].unsqueeze(-1).detach()
-    p_post, p_prev = r["prob_map_post"].unsqueeze(-1), r["prob_map_prev"].unsqueeze(-1)
-    if global_step <= decay_iteration * 1000:               # initialisation phase
-        pho = loss(r["rgb_map_ref_dy"], rgb_gt)
-        pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post)
-        pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev)
-    else:
-        pho = _masked_mean((r["rgb_map_ref_dy"] - rgb_gt) ** 2, dd)
-        pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post * dd)
-        pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev * dd)
-    if chain_5frames:
-        pho = pho + _masked_mean((r["rgb_map_pp_dy"] - rgb_gt) ** 2, dd)
-    logs["pho_loss"] = pho.detach()
-    combined = loss(r["rgb_map_ref"], rgb_gt)
-    logs["combined_loss"] = combined.detach()
+    if not rays_hip:
+        dd = r["weights_map_dd"].unsqueeze(-1).detach()
+        p_post, p_prev = r["prob_map_post"].unsqueeze(-1), r["prob_map_prev"].unsqueeze(-1)
+        if global_step <= decay_iteration * 1000:               # initialisation phase
+            pho = loss(r["rgb_map_ref_dy"], rgb_gt)
+            pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post)
+            pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev)
+        else:
+            pho = _masked_mean((r["rgb_map_ref_dy"] - rgb_gt) ** 2, dd)
+            pho = pho + _masked_mean((r["rgb_map_post_dy"] - rgb_gt) ** 2, p_post * dd)
+            pho = pho + _masked_mean((r["rgb_map_prev_dy"] - rgb_gt) ** 2, p_prev * dd)
+        if chain_5frames:
+            pho = pho + _masked_mean((r["rgb_map_pp_dy"] - rgb_gt) ** 2, dd)
+        logs["pho_loss"] = pho.detach()
+        combined = loss(r["rgb_map_ref"], rgb_gt)
+        logs["combined_loss"] = combined.detach()
 
     # the per-sample terms: one pair of launches
     l_cyc, l_prob, l_min, l_ent = (hp("lambda_cyc"), hp("lambda_prob_reg"), hp("lambda_sf_reg"), hp("lambda_blending_reg"))
@@ -216,6 +297,20 @@ def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_fr
     divisor = global_step // (decay_iteration * 1000)
     w_of = hp("lambda_optical_flow") / (10 ** divisor)
     w_depth = hp("lambda_sf_depth") / (10 ** divisor)
+
+    if rays_hip:                                             # the per-ray terms: the two projections, one pair of launches
+        def render(k, pts):                                  # k: 1 the next frame, 0 the previous
+            return zest_utils.projection_from_ndc(fnb_w2cs[:, k], H, W, focal, r["weights_ref_dy"], r[pts])
+        flow_fwd = render(1, "raw_pts_post") if frame_t != total_frames - 1 or frame_t == 0 else None
+        flow_bwd = render(0, "raw_pts_prev") if frame_t != 0 else None
+        rays, pho, combined, flow, depth = scene_flow_ray_terms(
+            rgb_gt, r["rgb_map_ref"], r["rgb_map_ref_dy"], r["rgb_map_post_dy"], r["rgb_map_prev_dy"],
+            r["rgb_map_pp_dy"] if chain_5frames else None, r["prob_map_post"], r["prob_map_prev"], r["weights_map_dd"],
+            flow_fwd, r["rays_flow_fwd_gt"], r["rays_mask_fwd_gt"], flow_bwd, r["rays_flow_bwd_gt"], r["rays_mask_bwd_gt"],
+            r["depth_map_ref_dy"], r["depth_gt"], global_step > decay_iteration * 1000, w_flow=w_of, w_depth=w_depth)
+        logs["pho_loss"], logs["combined_loss"] = pho, combined
+        logs["flow_loss"], logs["sf_depth_loss"] = w_of * flow, w_depth * depth
+        return rays + samples + regs, logs
 
     def flow_error(k, pts, gt, mask):                        # k: 1 the next frame, 0 the previous
         render = zest_utils.projection_from_ndc(fnb_w2cs[:, k], H, W, focal, r["weights_ref_dy"], r[pts])

@@ -365,6 +365,39 @@ int zest_sf_ray_bwd(const float *target, const float *rgb_ref, const float *rgb_
                     float *d_rgb_post_dy, float *d_rgb_prev_dy, float *d_rgb_pp_dy, float *d_prob_post,
                     float *d_prob_prev, float *d_flow_fwd, float *d_flow_bwd, float *d_depth, void *stream);
 
+/* Patch terms of the static ("svs") training step (reference train.py:599-617, 754, losses.py:20-51),
+ * one launch forward (a single workgroup that strides over the pixels: any P, H, W >= 1), one launch
+ * backward (one thread per pixel).
+ * rgb (the prediction), target: [P,H,W,3]; depth: [P,H,W]; all contiguous; a tensor no requested
+ * term reads may be NULL.  Differences are taken inside a row and inside a column of one patch only.
+ *   ZEST_PT_MSE     mean (rgb - target)^2 over the 3 P H W elements
+ *   ZEST_PT_TV      mean |d(y,x) - d(y,x+1)| over P H (W-1) + mean |d(y,x) - d(y+1,x)| over P (H-1) W
+ *                   (total_variation_loss)
+ *   ZEST_PT_SMOOTH  the same two means of |delta d| exp(-(1/3) sum_c |delta I_c|), delta I the same
+ *                   neighbour difference of rgb (get_disparity_smoothness); the gradient goes to
+ *                   depth and, through the weight, to rgb
+ * zest_patch_terms_fwd writes result [ZEST_PATCH_COLS]: 0 mse, 1 tv, 2 smooth, 0 where not
+ *   requested; 3 sum (rgb - target)^2; 4, 5 sum |delta d| along x, y; 6, 7 the weighted sums along
+ *   x, y; 8 c_mse mse + c_tv tv + c_smooth smooth.
+ * zest_patch_terms_bwd writes d (c_mse mse + c_tv tv + c_smooth smooth) / d tensor into d_rgb and
+ *   d_depth where they are not NULL, every element once (zeros where no requested term reads the
+ *   tensor).  The means have fixed counts: it takes nothing from the forward.  |0| has gradient 0,
+ *   for the depth difference and for each colour difference inside the weight.
+ * No atomics: two calls on the same inputs are bit-identical.
+ * Errors: P, H or W < 1; H < 2 or W < 2 with TV or SMOOTH (a mean over no element); an empty or
+ * unknown term mask; a NULL tensor that a requested term reads; a NULL result. */
+enum {
+    ZEST_PT_MSE = 1,
+    ZEST_PT_TV = 2,
+    ZEST_PT_SMOOTH = 4
+};
+#define ZEST_PATCH_COLS 9
+int zest_patch_terms_fwd(const float *rgb, const float *target, const float *depth, int terms, int P, int H,
+                         int W, float c_mse, float c_tv, float c_smooth, float *result, void *stream);
+int zest_patch_terms_bwd(const float *rgb, const float *target, const float *depth, int terms, int P, int H,
+                         int W, float c_mse, float c_tv, float c_smooth, float *d_rgb, float *d_depth,
+                         void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

@@ -416,6 +416,35 @@ class SceneFlowRayFn(Function):
         return tuple(by_pos.get(i) for i in range(len(zest_hip.SF_RAY_TENSORS))) + (None,) * 8
 
 
+class PatchTermsFn(Function):
+    """Patch terms of the static training step (csrc/patch_losses.hip).  rgb, target [P,H,W,3] and depth [P,H,W],
+    contiguous fp32 (None where no requested term reads one), then terms, the coefficients (c_mse, c_tv, c_smooth) and the
+    caller's torch.is_grad_enabled() (as SceneFlowRayFn) -> (total = c_mse mse + c_tv tv + c_smooth smooth, mse, tv,
+    smooth); only `total` carries the graph.  When rgb or depth requires a gradient and the graph is recorded both
+    launches happen here (the means have fixed counts: the second needs nothing from the first, so nothing is waited for
+    between them) and backward is the product with the upstream scalar; otherwise only the forward launch runs."""
+
+    @staticmethod
+    def forward(ctx, rgb, target, depth, terms, c_mse, c_tv, c_smooth, recording):
+        coeff = (c_mse, c_tv, c_smooth)
+        want = (bool(recording) and ctx.needs_input_grad[0] and rgb is not None,
+                bool(recording) and ctx.needs_input_grad[2] and depth is not None)
+        result = zest_hip.patch_terms_fwd(rgb, target, depth, terms, coeff)
+        mse, tv, smooth, total = result[0], result[1], result[2], result[zest_hip.PATCH_COLS - 1]
+        ctx.want = want
+        if any(want):
+            grads = zest_hip.patch_terms_bwd(rgb, target, depth, terms, coeff, want=want)
+            ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(mse, tv, smooth)
+        return total, mse, tv, smooth
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        saved = iter(ctx.saved_tensors)
+        g_rgb, g_depth = (next(saved) * g if w else None for w in ctx.want)
+        return g_rgb, None, g_depth, None, None, None, None, None
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

@@ -24,7 +24,7 @@ import runpy
 import sys
 import types
 
-__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "main"]
+__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -43,6 +43,8 @@ _REIMPORTED = {
 }
 # opt-in (install(sf_losses=True) / ZEST_DROPIN_SF_LOSSES=1): the scene-flow regularisers, one HIP launch per call
 SF_LOSS_NAMES = ("compute_sf_smooth_loss", "compute_sf_lke_loss")
+# opt-in (install(patch_losses=True) / ZEST_DROPIN_PATCH_LOSSES=1): the image-space regularisers of the static step
+PATCH_LOSS_NAMES = ("total_variation_loss", "get_disparity_smoothness")
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -66,11 +68,12 @@ def _bind(mod, name, value):
 
 
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False):
+            sf_losses=False, patch_losses=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
-    they stay the caller's).
+    they stay the caller's).  patch_losses: also rebind `losses.total_variation_loss` and
+    `losses.get_disparity_smoothness` (off by default likewise).
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +94,8 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
         zest_name, names = PATH_NAMES[name]
         if name == "losses" and sf_losses:
             names = names + SF_LOSS_NAMES
+        if name == "losses" and patch_losses:
+            names = names + PATCH_LOSS_NAMES
         target = targets[name]
         zest = importlib.import_module(zest_name)
         for n in names:
@@ -121,10 +126,12 @@ def main(argv=None):
         print("usage: python -m zest_dropin SCRIPT.py [script arguments]\n"
               "runs SCRIPT (e.g. the reference's train.py / test.py) with the MI355X rendering path bound into its "
               "own networks / utils / renderer / losses modules; ZEST_DROPIN_SF_LOSSES=1 also binds the scene-flow "
-              "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss)")
+              "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss), ZEST_DROPIN_PATCH_LOSSES=1 the patch "
+              "regularisers of the static step (total_variation_loss, get_disparity_smoothness)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
-    install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1")
+    install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
+            patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

@@ -85,6 +85,8 @@ _SIGS = {
     "zest_sf_sample_bwd": (_i, [_vp] * 8 + [_i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 8 + [_vp]),
     "zest_sf_ray_fwd": (_i, [_vp] * 17 + [_i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp]),
     "zest_sf_ray_bwd": (_i, [_vp] * 17 + [_i, _i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 10 + [_vp]),
+    "zest_patch_terms_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "zest_patch_terms_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -507,6 +509,77 @@ def sf_ray_bwd(tensors, totals, terms=SFR_ALL, late_phase=False, five_frames=Tru
     c = [float(v) for v in coeff]
     _check(lib().zest_sf_ray_bwd(*[_ptr(t) for t in tensors], terms, int(bool(late_phase)), int(bool(five_frames)), R,
                                  _ptr(totals), *c, *[_ptr(g) for g in out], _stream(first)), "zest_sf_ray_bwd")
+    return out
+
+PT_MSE, PT_TV, PT_SMOOTH = 1, 2, 4
+PT_ALL = PT_MSE | PT_TV | PT_SMOOTH
+PATCH_COLS = 9
+# launch geometry of csrc/patch_losses.hip (kFwdThreads, kBwdThreads), no part of the C ABI: kept here for the tests,
+# which choose their sizes either side of it
+PATCH_FWD_THREADS, PATCH_BWD_THREADS = 1024, 256
+# the tensors of the patch terms, in the order of the C ABI: name, trailing extent (0: none), the terms that read it,
+# whether it takes a gradient
+PATCH_TENSORS = (("rgb", 3, PT_MSE | PT_SMOOTH, True), ("target", 3, PT_MSE, False), ("depth", 0, PT_TV | PT_SMOOTH, True))
+
+
+def _patch_inputs(who, rgb, target, depth, terms):
+    """Shape, dtype, device and contiguity of the three tensors (None where no requested term reads one), checked before
+    the library is touched -> (P, H, W, terms)."""
+    terms = int(terms)
+    if terms <= 0 or terms & ~PT_ALL:
+        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
+    tensors = (rgb, target, depth)
+    for t, (name, _, readers, _) in zip(tensors, PATCH_TENSORS):
+        if t is None and terms & readers:
+            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
+    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
+    lead = tuple(first.shape[:3])
+    if len(lead) != 3 or min(lead) < 1:
+        raise RuntimeError("zest_hip: %s needs [P,H,W(,3)] with P, H, W >= 1, got %s" % (who, tuple(first.shape)))
+    if terms & (PT_TV | PT_SMOOTH) and min(lead[1:]) < 2:
+        raise RuntimeError("zest_hip: %s: terms 0x%x take neighbour differences, %s leaves a mean over no element"
+                           % (who, terms, tuple(first.shape)))
+    for t, (name, last, _, _) in zip(tensors, PATCH_TENSORS):
+        if t is None:
+            continue
+        want = lead + ((last,) if last else ())
+        if not t.is_cuda:
+            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
+                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
+    return lead + (terms,)
+
+
+def patch_terms_fwd(rgb, target, depth, terms=PT_ALL, coeff=(1.0, 1.0, 1.0)):
+    """Patch terms of the static training step, forward launch.  rgb, target [P,H,W,3], depth [P,H,W], contiguous fp32
+    (None where no requested term reads one) -> result [PATCH_COLS]: mse, tv, smooth, the five sums they come from, last
+    c_mse mse + c_tv tv + c_smooth smooth for coeff = (c_mse, c_tv, c_smooth) (include/zest_render.h names the columns)."""
+    P, H, W, terms = _patch_inputs("patch_terms_fwd", rgb, target, depth, terms)
+    first = next(t for t in (rgb, target, depth) if t is not None)
+    result = torch.empty(PATCH_COLS, device=first.device, dtype=torch.float32)
+    _check(lib().zest_patch_terms_fwd(_ptr(rgb), _ptr(target), _ptr(depth), terms, P, H, W, *[float(v) for v in coeff],
+                                      _ptr(result), _stream(first)), "zest_patch_terms_fwd")
+    return result
+
+
+def patch_terms_bwd(rgb, target, depth, terms=PT_ALL, coeff=(1.0, 1.0, 1.0), want=(True, True), grads=None):
+    """Backward launch -> (d_rgb, d_depth), the gradients of c_mse mse + c_tv tv + c_smooth smooth (None where `want`
+    is false or the tensor is None; zeros where no requested term reads the tensor).  grads: optional preallocated
+    tensors (or None) to write into; every element of them is written."""
+    P, H, W, terms = _patch_inputs("patch_terms_bwd", rgb, target, depth, terms)
+    first = next(t for t in (rgb, target, depth) if t is not None)
+    out = []
+    for k, t in enumerate((rgb, depth)):
+        g = None
+        if want[k] and t is not None:
+            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
+            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
+                raise RuntimeError("zest_hip: patch_terms_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
+                                   % (k, tuple(t.shape), first.device))
+        out.append(g)
+    _check(lib().zest_patch_terms_bwd(_ptr(rgb), _ptr(target), _ptr(depth), terms, P, H, W, *[float(v) for v in coeff],
+                                      _ptr(out[0]), _ptr(out[1]), _stream(first)), "zest_patch_terms_bwd")
     return out
 
 

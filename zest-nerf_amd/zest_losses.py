@@ -20,7 +20,14 @@ MVSNeRFSystem.train_sf_step, train.py:346-585) on top of these pieces and `zest_
 error, the optical-flow error and the whitened depth prior with its two medians (train.py:395-430, 512-575,
 losses.py:89-140) - in two launches of csrc/sf_ray_losses.hip, values and gradients; `train_sf_step_loss` routes
 them there (`ray_terms="hip"`, the default) or through the torch composition it had before (`ray_terms="torch"`).
-The other names of the reference's losses.py are image-space terms outside this path.
+
+`total_variation_loss` and `get_disparity_smoothness` keep the reference's signatures (losses.py:20-51); `patch_terms`
+evaluates what the static ("svs") training step evaluates on its rendered patches - reconstruction error, total
+variation of the depth patch, edge-aware depth smoothness and the PSNR it logs (train.py:599-617, 754) - in two launches
+of csrc/patch_losses.hip, values and gradients; `train_step_loss` is the part of MVSNeRFSystem.training_step
+(train.py:587-760) this package evaluates, on top of `patch_terms` and `distortion_loss`.  The adversarial and
+perceptual terms of that step need the caller's discriminator and a pretrained network: they stay the caller's, as do
+`mse_masked`, `mae_masked` and `compute_depth_loss` as names (the scene-flow step evaluates them inside its kernels).
 """
 import torch
 
@@ -29,7 +36,8 @@ import zest_hip
 import zest_utils
 
 __all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers",
-           "scene_flow_sample_terms", "scene_flow_ray_terms", "train_sf_step_loss"]
+           "scene_flow_sample_terms", "scene_flow_ray_terms", "train_sf_step_loss", "total_variation_loss",
+           "get_disparity_smoothness", "patch_terms", "train_step_loss"]
 
 
 def distortion_loss(ray_weights, t_vals):
@@ -327,3 +335,138 @@ def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_fr
     logs["sf_depth_loss"] = (w_depth * depth).detach()
 
     return pho + combined + samples + regs + w_of * flow + w_depth * depth, logs
+
+
+def _patches(who, named):
+    """Check the patch tensors BEFORE the library is touched and return them as contiguous fp32.  named: [(argument
+    name, tensor [B,H,W] or [B,H,W,last], last or 0)]; B, H and W agree.  Shapes first, then the batch (empty; too small
+    for a neighbour difference), then the device."""
+    first_name, first, _ = named[0]
+    for name, t, last in named:
+        if not torch.is_tensor(t) or t.dim() != (4 if last else 3) or (last and t.shape[-1] != last):
+            raise RuntimeError("%s: %s must be a tensor [B, H, W%s], got %s"
+                               % (who, name, ", %d" % last if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if t.shape[:3] != first.shape[:3]:
+            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
+    if first.numel() == 0:
+        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
+    if min(first.shape[1:3]) < 2:
+        raise RuntimeError("%s: patches of %d x %d leave no neighbour difference in one direction (the mean over no "
+                           "element is undefined)" % (who, first.shape[1], first.shape[2]))
+    for name, t, _ in named:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if t.device != first.device:
+            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
+    return [t.contiguous().float() for _, t, _ in named]
+
+
+def total_variation_loss(image):
+    """Total variation of image [B,H,W]: mean |image(y,x) - image(y,x+1)| + mean |image(y,x) - image(y+1,x)| -> scalar."""
+    (d,) = _patches("total_variation_loss", [("image", image, 0)])
+    return zest_autograd.PatchTermsFn.apply(None, None, d, zest_hip.PT_TV, 0.0, 1.0, 0.0, torch.is_grad_enabled())[0]
+
+
+def get_disparity_smoothness(disp, img):
+    """Edge-aware smoothness of disp [B,H,W,1] under img [B,H,W,3]: the two means of total_variation_loss with every
+    difference of disp weighted by exp(-mean_c |the same difference of img|) -> scalar.  The gradient goes to disp and,
+    through the weights, to img."""
+    d, c = _patches("get_disparity_smoothness", [("disp", disp, 1), ("img", img, 3)])
+    return zest_autograd.PatchTermsFn.apply(c, None, d.reshape(d.shape[:3]), zest_hip.PT_SMOOTH, 0.0, 0.0, 1.0,
+                                            torch.is_grad_enabled())[0]
+
+
+def patch_terms(rgb_pred, rgb_gt, depth_pred, patch_size, w_rec=1.0, w_tv=0.0, w_smooth=0.0):
+    """The terms of one static training step on its rendered patches, values and gradients from two launches:
+        mse    = mean (rgb_pred - rgb_gt)^2                                                          (train.py:602)
+        tv     = total_variation_loss(depth patches)                                                 (train.py:607-608)
+        smooth = get_disparity_smoothness(depth patches, rgb_pred patches)                           (train.py:614-616)
+        psnr   = 10 log10(1 / mse)                                                                   (train.py:754)
+    rgb_pred, rgb_gt: [..., R, 3], depth_pred: [..., R], R a multiple of patch_size^2; the rays are cut into patches of
+    patch_size x patch_size in their order, as the reference's reshape does.  A weight of 0 drops its term (its value
+    comes back as 0; psnr is None without the reconstruction term); one of them must not be 0.
+    -> (w_rec mse + w_tv tv + w_smooth smooth, with the graph; mse, tv, smooth, detached; psnr)."""
+    terms = (zest_hip.PT_MSE if w_rec else 0) | (zest_hip.PT_TV if w_tv else 0) | (zest_hip.PT_SMOOTH if w_smooth else 0)
+    if not terms:
+        raise RuntimeError("patch_terms: every weight is 0: no term to evaluate")
+    return _patch_terms("patch_terms", rgb_pred, rgb_gt, depth_pred, patch_size, terms, w_rec, w_tv, w_smooth)
+
+
+def _patch_terms(who, rgb_pred, rgb_gt, depth_pred, patch_size, terms, w_rec, w_tv, w_smooth):
+    """patch_terms with the term mask given (a term may be in it with the weight 0: evaluated, not part of the total).
+    Shapes first, then the batch and the patch size, then the device: all BEFORE the library is touched."""
+    named = [("rgb_pred", rgb_pred, 3), ("rgb_gt", rgb_gt, 3), ("depth_pred", depth_pred, 0)]
+    for name, t, last in named:
+        if not torch.is_tensor(t) or t.dim() < (2 if last else 1) or (last and t.shape[-1] != last):
+            raise RuntimeError("%s: %s must be a tensor [..., N_rays%s], got %s"
+                               % (who, name, ", 3" if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if (t.shape[:-1] if last else t.shape) != rgb_pred.shape[:-1]:
+            raise RuntimeError("%s: %s %s does not match rgb_pred %s" % (who, name, tuple(t.shape), tuple(rgb_pred.shape)))
+    if rgb_pred.numel() == 0:
+        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(rgb_pred.shape)))
+    ps = int(patch_size)
+    if ps < 2:
+        raise RuntimeError("%s: patch_size %d < 2 leaves no neighbour difference" % (who, ps))
+    if rgb_pred.shape[-2] % (ps * ps):
+        raise RuntimeError("%s: %d rays are not a multiple of patch_size^2 = %d" % (who, rgb_pred.shape[-2], ps * ps))
+    for name, t, _ in named:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if t.device != rgb_pred.device:
+            raise RuntimeError("%s: %s is on %s, rgb_pred on %s" % (who, name, t.device, rgb_pred.device))
+    rgb = rgb_pred.contiguous().float().reshape(-1, ps, ps, 3) if terms & (zest_hip.PT_MSE | zest_hip.PT_SMOOTH) else None
+    gt = rgb_gt.detach().contiguous().float().reshape(-1, ps, ps, 3) if terms & zest_hip.PT_MSE else None
+    depth = depth_pred.contiguous().float().reshape(-1, ps, ps) if terms & (zest_hip.PT_TV | zest_hip.PT_SMOOTH) else None
+    total, mse, tv, smooth = zest_autograd.PatchTermsFn.apply(rgb, gt, depth, terms, float(w_rec), float(w_tv),
+                                                              float(w_smooth), torch.is_grad_enabled())
+    return total, mse, tv, smooth, -10.0 * torch.log10(mse) if terms & zest_hip.PT_MSE else None
+
+
+def train_step_loss(results, hparams, adversarial=False):
+    """The part of one static ("svs") training step that this package evaluates: MVSNeRFSystem.training_step
+    (train.py:587-760) without its class, its discriminators and its perceptual network.
+    results: what the model returned; read are rgb_map [..., R, 3], target_s [..., R, 3], depth_map [..., R],
+    weights [1, R, S] and t_vals (the last two only with_distortion_loss).  hparams (attributes or keys): patch_size,
+    with_depth_loss_reg / lambda_depth_reg (total variation of the depth patches), with_depth_smoothness /
+    lambda_depth_smooth, with_distortion_loss / lambda_distortion, and lambda_rec if adversarial.
+      adversarial=False: the loss of plain training (gan_type None, train.py:742-748),
+          mse + l_reg (l_reg tv) + l_smooth (l_smooth smooth) + l_dist (l_dist distortion):
+          the reference multiplies every regulariser by its coefficient where it computes and logs it and AGAIN in the
+          total.  That is what the reference trains with, so it is what this function returns.
+      adversarial=True: the terms of the generator step (optimizer_idx 0, train.py:683-694) that need no network,
+          l_rec mse + l_reg tv + l_smooth smooth + l_dist distortion; the caller adds G_fake_loss, the feature-matching
+          and the perceptual term.
+    hparams.train_sceneflow must be false (that step is train_sf_step_loss).  with_perceptual_loss, with_depth_loss_rec
+    and the depth discriminator are not evaluated here and are ignored: their terms are the caller's to add.
+    -> (loss with the graph, {name: logged value}) with the reference's names, weighted as it logs them: tv_depth_loss,
+    depth_smooth_loss, distortion_loss (each where its flag is set), G_rec_loss (adversarial only) and train_PSNR =
+    10 log10(1 / mse)."""
+    if isinstance(hparams, dict):
+        hp = hparams.__getitem__
+    else:
+        def hp(name):
+            return getattr(hparams, name)
+    if hp("train_sceneflow"):
+        raise RuntimeError("train_step_loss: hparams.train_sceneflow is set: that step's loss is train_sf_step_loss")
+    l_reg = float(hp("lambda_depth_reg")) if hp("with_depth_loss_reg") else 0.0
+    l_smooth = float(hp("lambda_depth_smooth")) if hp("with_depth_smoothness") else 0.0
+    l_dist = float(hp("lambda_distortion")) if hp("with_distortion_loss") else 0.0
+    l_rec = float(hp("lambda_rec")) if adversarial else 1.0
+    again = (lambda c: c) if adversarial else (lambda c: c * c)      # plain training applies the coefficients twice
+    # the reconstruction error is always in the mask: train_PSNR needs it even where lambda_rec is 0
+    terms = zest_hip.PT_MSE | (zest_hip.PT_TV if l_reg else 0) | (zest_hip.PT_SMOOTH if l_smooth else 0)
+    total, mse, tv, smooth, psnr = _patch_terms("train_step_loss", results["rgb_map"], results["target_s"], results["depth_map"],
+                                                hp("patch_size"), terms, l_rec, again(l_reg), again(l_smooth))
+    logs = {}
+    if hp("with_depth_loss_reg"):
+        logs["tv_depth_loss"] = l_reg * tv
+    if hp("with_depth_smoothness"):
+        logs["depth_smooth_loss"] = l_smooth * smooth
+    if hp("with_distortion_loss"):
+        dist = distortion_loss(results["weights"], results["t_vals"])
+        logs["distortion_loss"] = l_dist * dist.detach()
+        total = total + again(l_dist) * dist
+    if adversarial:
+        logs["G_rec_loss"] = l_rec * mse
+    logs["train_PSNR"] = psnr
+    return total, logs

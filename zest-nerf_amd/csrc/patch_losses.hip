@@ -24,8 +24,6 @@ constexpr int kAllTerms = ZEST_PT_MSE | ZEST_PT_TV | ZEST_PT_SMOOTH;
 enum { C_MSE, C_TV, C_SMOOTH, C_MSE_SUM, C_TV_X, C_TV_Y, C_SMOOTH_X, C_SMOOTH_Y, C_TOTAL };
 static_assert(C_TOTAL + 1 == kCols, "ZEST_PATCH_COLS");
 
-__device__ __forceinline__ float sign0(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }   // sign(0) = 0
-
 // exp(-(1/3) sum_c |a_c - b_c|) of two pixels' colours
 __device__ __forceinline__ float edge_weight(const float *a, const float *b) {
     return expf(-(fabsf(a[0] - b[0]) + fabsf(a[1] - b[1]) + fabsf(a[2] - b[2])) * (1.0f / 3.0f));
@@ -37,7 +35,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_terms_fwd_kernel(const floa
                                                                        float c_smooth, float *__restrict__ result) {
     __shared__ float red[kFwdWaves][kSums];
     __shared__ float sums[kSums];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const bool mse = terms & ZEST_PT_MSE, tv = terms & ZEST_PT_TV, smooth = terms & ZEST_PT_SMOOTH;
 
     float acc[kSums] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};     // squared error; |delta d| along x, y; the weighted ones along x, y
@@ -62,19 +60,7 @@ __global__ __launch_bounds__(kFwdThreads) void patch_terms_fwd_kernel(const floa
             }
         }
     }
-    // the workgroup's sums in a fixed order: lanes of a wave, then the waves in turn
-#pragma unroll
-    for (int k = 0; k < kSums; k++) {
-        const float v = wave_sum(acc[k]);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < kSums) {
-        float v = 0.0f;
-        for (int w = 0; w < kFwdWaves; w++) v += red[w][tid];
-        sums[tid] = v;
-    }
-    __syncthreads();
+    block_sums<kSums, kFwdWaves>(acc, red, sums);
     if (tid == 0) {
         const float v_mse = mse ? sums[0] / (3.0f * (float)n_pix) : 0.0f;
         const float v_tv = tv ? sums[1] / n_x + sums[2] / n_y : 0.0f;

@@ -35,8 +35,6 @@ __device__ __forceinline__ Euc euclid(const float *__restrict__ p, float H, floa
     return o;
 }
 
-__device__ __forceinline__ float sign0(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }   // sign(0) = 0
-
 // tensors: 0 ref, 1 post, 2 prev, 3 pp.  c_sp = w_sp * scale_sp, c_st = w_st * scale_st: the gradient written is
 // d (w_sp * spatial + w_st * temporal) / d tensor.
 __global__ __launch_bounds__(kWaves * 64) void sf_reg_kernel(

@@ -44,8 +44,6 @@ struct RayGrad {
     float *rgb[5], *prob[2], *flow[2], *depth;
 };
 
-__device__ __forceinline__ float sign0(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }   // sign(0) = 0
-
 // unsigned keys in the order of the floats
 __device__ __forceinline__ unsigned ordered_key(float v) {
     const unsigned u = __float_as_uint(v);
@@ -59,25 +57,6 @@ __device__ __forceinline__ float key_value(unsigned k) {
 __device__ __forceinline__ float pho_mask(int j, bool late, float p_post, float p_prev, float dd) {
     const float base = j == 1 ? p_post : j == 2 ? p_prev : j == 3 ? dd : 1.0f;
     return (late && j < 3) ? base * dd : base;
-}
-
-// sums of acc[0..N) over the workgroup, in a fixed order, left in out[0..N) for every thread to read
-template <int N>
-__device__ __forceinline__ void block_sums(float (&acc)[N], float (*red)[kMaxSums], float *out) {
-    static_assert(N <= kMaxSums, "kMaxSums");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        const float v = wave_sum(acc[k]);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        float v = 0.0f;
-        for (int w = 0; w < kFwdWaves; w++) v += red[w][threadIdx.x];
-        out[threadIdx.x] = v;
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(kFwdThreads) void sf_ray_fwd_kernel(RayIn in, int terms, int late_i, int five_i, int R,
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(kFwdThreads) void sf_ray_fwd_kernel(RayIn in, int t
             }
         }
     }
-    block_sums(acc, red, sums);
+    block_sums<kMaxSums, kFwdWaves>(acc, red, sums);
 
     // ---- the whitened depth prior
     float depth_value = 0.0f;
@@ -186,7 +165,7 @@ __global__ __launch_bounds__(kFwdThreads) void sf_ray_fwd_kernel(RayIn in, int t
             if (first == R && ordered_key(a) == med_key) first = (int)r;
         }
         if (first < R) atomicMin(&med_index, first);
-        block_sums(dev, red, dsum);
+        block_sums<3, kFwdWaves>(dev, red, dsum);
         const float scale[2] = {dsum[0] / (float)R, dsum[1] / (float)R};
         float err[3] = {0.0f, 0.0f, 0.0f};                     // sum d^2, sum d, sum d wa;  d = wa - wb
         for (long long r = tid; r < R; r += kFwdThreads) {
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(kFwdThreads) void sf_ray_fwd_kernel(RayIn in, int t
             err[1] += d;
             err[2] += d * wa;
         }
-        block_sums(err, red, esum);
+        block_sums<3, kFwdWaves>(err, red, esum);
         if (tid == 0) {
             result[C_MED] = med[0], result[C_MED + 1] = scale[0], result[C_MED + 2] = med[1], result[C_MED + 3] = scale[1];
             result[C_DEPTH_G] = esum[1], result[C_DEPTH_Q] = esum[2], result[C_DEPTH_SIGN] = dsum[2];

@@ -28,8 +28,6 @@ struct SampleGrad {
     float *sf[4], *prob[2], *w, *blend;
 };
 
-__device__ __forceinline__ float sign0(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }   // sign(0) = 0
-
 // partials row: 0 N_post, 1 M_post, 2 N_prev, 3 M_prev (M = sum_s m), 4 sum |prob_post|, 5 sum |prob_prev|,
 // 6 sum_s |w_s sum_c sf_ref2post|, 7 the same of ref2prev, 8 sum -b log(b + 1e-8).  Columns of terms not requested are 0.
 __global__ __launch_bounds__(kWaves * 64) void sf_sample_fwd_kernel(SampleIn in, int terms, int R, int S,

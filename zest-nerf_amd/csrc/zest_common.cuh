@@ -56,6 +56,27 @@ __device__ __forceinline__ float seg_scan_mul(float v, int lane_in_seg) {
     return v;
 }
 
+// sums of acc[0..N) over a workgroup of WAVES waves, in a fixed order (the lanes of a wave, then the waves in turn: two
+// launches are bit-identical), left in out[0..N) for every thread to read.  red: WAVES rows of STRIDE >= N floats of LDS;
+// out: LDS.  Every thread of the workgroup calls it: both barriers are outside any branch.
+template <int N, int WAVES, int STRIDE>
+__device__ __forceinline__ void block_sums(float (&acc)[N], float (*red)[STRIDE], float *out) {
+    static_assert(N <= STRIDE, "a row of `red` holds one wave's N sums");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const float v = wave_sum(acc[k]);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        float v = 0.0f;
+        for (int w = 0; w < WAVES; w++) v += red[w][threadIdx.x];
+        out[threadIdx.x] = v;
+    }
+    __syncthreads();
+}
+
 // ---- DPP forms for a 32-lane half (plain VALU: no LDS round trip per step) --------------------
 // dpp_ctrl: quad_perm[1,0,3,2]=0xB1, quad_perm[2,3,0,1]=0x4E, row_half_mirror=0x141,
 // row_mirror=0x140, row_shr:n=0x110+n, row_bcast:15=0x142, wave_shr:1=0x138
@@ -96,6 +117,7 @@ __device__ __forceinline__ float lower_half_excl_prod(float f, int col, float *t
 
 // ---- scalar math ---------------------------------------------------------------------
 __device__ __forceinline__ float zest_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float sign0(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }   // sign(0) = 0
 
 // sin and cos of a moderate fp32 argument, <1 ulp: three-term Cody-Waite reduction by
 // pi/2 with FMAs, near-minimax polynomials on [-pi/4, pi/4].  Arguments on this path are

@@ -88,13 +88,25 @@ class EncodePairFn(Function):
         return g_a, g_b, g_vol_cl, None, None, None, None, None
 
 
+def _param_table(slots, params, detach=False):
+    """The 2 * P_COUNT (weight, bias) table of the C ABI (ZEST_P_* order) from the tensors of the slots in `slots`."""
+    table = [None] * (2 * zest_hip.P_COUNT)
+    for i, s in enumerate(slots):
+        w, b = params[2 * i], params[2 * i + 1]
+        table[2 * s], table[2 * s + 1] = (w.detach(), b.detach()) if detach else (w, b)
+    return table
+
+
+def _slot_grads(slots, grads):
+    """The (weight, bias) gradients of the slots in `slots`, in the order of their parameters, out of the table `grads`."""
+    return [grads[2 * s + k] for s in slots for k in (0, 1)]
+
+
 class MlpFn(Function):
     @staticmethod
     def forward(ctx, x, desc, slots, *params):
         """params: the (weight, bias) tensors of the slots in `slots` (ZEST_P_* order)."""
-        table = [None] * (2 * zest_hip.P_COUNT)
-        for i, s in enumerate(slots):
-            table[2 * s], table[2 * s + 1] = params[2 * i], params[2 * i + 1]
+        table = _param_table(slots, params)
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         out, saved = zest_hip.mlp_train_fwd(desc, table, x2)
@@ -105,16 +117,11 @@ class MlpFn(Function):
     @staticmethod
     def backward(ctx, g_out):
         x2, saved, out, *params = ctx.saved_tensors
-        table = [None] * (2 * zest_hip.P_COUNT)
-        for i, s in enumerate(ctx.slots):
-            table[2 * s], table[2 * s + 1] = params[2 * i], params[2 * i + 1]
+        table = _param_table(ctx.slots, params)
         g_x, grads = zest_hip.mlp_train_bwd(ctx.desc, table, x2, saved, out,
                                             g_out.reshape(-1, ctx.desc.out_ch).contiguous(),
                                             want_gx=ctx.needs_input_grad[0])
-        gp = []
-        for s in ctx.slots:
-            gp += [grads[2 * s], grads[2 * s + 1]]
-        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, *gp)
+        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, *_slot_grads(ctx.slots, grads))
 
 
 class MlpFn16(Function):
@@ -126,9 +133,7 @@ class MlpFn16(Function):
 
     @staticmethod
     def forward(ctx, x, desc, slots, shared, *params):
-        table = [None] * (2 * zest_hip.P_COUNT)
-        for i, s in enumerate(slots):
-            table[2 * s], table[2 * s + 1] = params[2 * i].detach(), params[2 * i + 1].detach()
+        table = _param_table(slots, params, detach=True)
         lead = x.shape[:-1]
         x2 = x.detach().reshape(-1, x.shape[-1]).contiguous()
         if shared is None:
@@ -143,18 +148,13 @@ class MlpFn16(Function):
     @staticmethod
     def backward(ctx, g_out):
         x2, stash, out, *params = ctx.saved_tensors
-        table = [None] * (2 * zest_hip.P_COUNT)
-        for i, s in enumerate(ctx.slots):
-            table[2 * s], table[2 * s + 1] = params[2 * i].detach(), params[2 * i + 1].detach()
+        table = _param_table(ctx.slots, params, detach=True)
         if "bwd" not in ctx.shared:
             ctx.shared["bwd"] = zest_hip.mlp_train16_pack_bwd(ctx.desc, table)
         g_x, grads, ctx.shared["work"] = zest_hip.mlp_train16_bwd(
             ctx.desc, ctx.shared["bwd"], table, x2, stash, out, g_out.reshape(-1, ctx.desc.out_ch).contiguous(),
             work=ctx.shared.get("work"))
-        gp = []
-        for s in ctx.slots:
-            gp += [grads[2 * s], grads[2 * s + 1]]
-        return (g_x.view(*ctx.lead, -1) if ctx.needs_input_grad[0] else None, None, None, None, *gp)
+        return (g_x.view(*ctx.lead, -1) if ctx.needs_input_grad[0] else None, None, None, None, *_slot_grads(ctx.slots, grads))
 
 
 class CompositeFn(Function):
@@ -329,6 +329,19 @@ class DistortionFn(Function):
         return grad * g, None
 
 
+def _save_grads(ctx, want, grads):
+    """Keep the gradients a loss Function computed in its forward: want[k] says whether input k of the backward launch
+    takes one, grads holds them (None elsewhere; empty when none is wanted and the launch was left out)."""
+    ctx.want = want
+    ctx.save_for_backward(*[g for g in grads if g is not None])
+
+
+def _scaled_grads(ctx, g):
+    """The gradients _save_grads kept, times the upstream scalar: one entry per entry of `want`, None where false."""
+    saved = iter(ctx.saved_tensors)
+    return tuple(next(saved) * g if w else None for w in ctx.want)
+
+
 class SceneFlowRegFn(Function):
     """Scene-flow regularisers (csrc/sf_losses.hip): values and the gradients of w_sp * spatial + w_st * temporal with
     respect to the point tensors from one HIP launch.  ref / post / prev / pp: [R,S,3] (None where no term reads the
@@ -338,8 +351,7 @@ class SceneFlowRegFn(Function):
     def forward(ctx, ref, post, prev, pp, terms, H, W, focal, w_sp, w_st):
         want = tuple(ctx.needs_input_grad[:4])                  # gradient buffers only where autograd asks for one
         loss_ray, grads = zest_hip.sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp, w_st, want=want)
-        ctx.want = want
-        ctx.save_for_backward(*[g for g in grads if g is not None])
+        _save_grads(ctx, want, grads)
         parts = loss_ray.sum(0)
         sp, st = parts[0], parts[1]
         ctx.mark_non_differentiable(sp, st)
@@ -347,8 +359,7 @@ class SceneFlowRegFn(Function):
 
     @staticmethod
     def backward(ctx, g, g_sp, g_st):
-        saved = iter(ctx.saved_tensors)
-        return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 6
+        return _scaled_grads(ctx, g) + (None,) * 6
 
 
 class SceneFlowSampleFn(Function):
@@ -371,18 +382,15 @@ class SceneFlowSampleFn(Function):
         prob_reg = totals[4:6].sum() / float(R * S)
         sf_min = totals[6:8].sum() / float(R * S)
         entropy = totals[8] / float(R * S)
-        ctx.want = want
-        if any(want):
-            grads = zest_hip.sf_sample_bwd(tensors, totals, terms, coeff, want=want)
-            ctx.save_for_backward(*[g for g in grads if g is not None])
+        grads = zest_hip.sf_sample_bwd(tensors, totals, terms, coeff, want=want) if any(want) else ()
+        _save_grads(ctx, want, grads)
         ctx.mark_non_differentiable(cycle, prob_reg, sf_min, entropy)
         total = coeff[0] * cycle + coeff[1] * prob_reg + coeff[2] * sf_min + coeff[3] * entropy
         return total, cycle, prob_reg, sf_min, entropy
 
     @staticmethod
     def backward(ctx, g, *unused):
-        saved = iter(ctx.saved_tensors)
-        return tuple(next(saved) * g if w else None for w in ctx.want) + (None,) * 5
+        return _scaled_grads(ctx, g) + (None,) * 5
 
 
 class SceneFlowRayFn(Function):
@@ -402,17 +410,14 @@ class SceneFlowRayFn(Function):
         want = tuple(bool(recording) and ctx.needs_input_grad[i] for i in zest_hip.SF_RAY_GRADS)
         result = zest_hip.sf_ray_fwd(tensors, terms, late_phase, five_frames, coeff)
         pho, combined, flow, depth, total = result[0], result[1], result[2], result[3], result[zest_hip.SF_RAY_COLS - 1]
-        ctx.want = want
-        if any(want):
-            grads = zest_hip.sf_ray_bwd(tensors, result, terms, late_phase, five_frames, coeff, want=want)
-            ctx.save_for_backward(*[g for g in grads if g is not None])
+        grads = zest_hip.sf_ray_bwd(tensors, result, terms, late_phase, five_frames, coeff, want=want) if any(want) else ()
+        _save_grads(ctx, want, grads)
         ctx.mark_non_differentiable(pho, combined, flow, depth)
         return total, pho, combined, flow, depth
 
     @staticmethod
     def backward(ctx, g, *unused):
-        saved = iter(ctx.saved_tensors)
-        by_pos = dict(zip(zest_hip.SF_RAY_GRADS, (next(saved) * g if w else None for w in ctx.want)))
+        by_pos = dict(zip(zest_hip.SF_RAY_GRADS, _scaled_grads(ctx, g)))
         return tuple(by_pos.get(i) for i in range(len(zest_hip.SF_RAY_TENSORS))) + (None,) * 8
 
 
@@ -431,17 +436,14 @@ class PatchTermsFn(Function):
                 bool(recording) and ctx.needs_input_grad[2] and depth is not None)
         result = zest_hip.patch_terms_fwd(rgb, target, depth, terms, coeff)
         mse, tv, smooth, total = result[0], result[1], result[2], result[zest_hip.PATCH_COLS - 1]
-        ctx.want = want
-        if any(want):
-            grads = zest_hip.patch_terms_bwd(rgb, target, depth, terms, coeff, want=want)
-            ctx.save_for_backward(*[g for g in grads if g is not None])
+        grads = zest_hip.patch_terms_bwd(rgb, target, depth, terms, coeff, want=want) if any(want) else ()
+        _save_grads(ctx, want, grads)
         ctx.mark_non_differentiable(mse, tv, smooth)
         return total, mse, tv, smooth
 
     @staticmethod
     def backward(ctx, g, *unused):
-        saved = iter(ctx.saved_tensors)
-        g_rgb, g_depth = (next(saved) * g if w else None for w in ctx.want)
+        g_rgb, g_depth = _scaled_grads(ctx, g)
         return g_rgb, None, g_depth, None, None, None, None, None
 
 

@@ -322,6 +322,57 @@ SF_SPATIAL = SF_SMOOTH_REF_POST | SF_SMOOTH_REF_PREV
 SF_TEMPORAL = SF_LKE_REF | SF_LKE_CHAIN_BWD | SF_LKE_CHAIN_FWD
 
 
+def _term_inputs(who, tensors, table, terms, all_terms, lead_rank, lead_check, gates=None):
+    """The checks the loss-kernel families share, made before the library is touched.  tensors: as given, None where no
+    requested term reads one; table: rows (name, trailing extent or 0, terms that read it, ...) in the order of the C ABI;
+    lead_rank: the leading extents all tensors share ([R,S]: 2, [R]: 1, [P,H,W]: 3); lead_check(who, terms, first, lead):
+    the family's own refusals of the leading shape; gates: name -> whether the terms read that tensor at all in this call
+    -> (the first tensor given, lead, terms).  In turn: the mask, a missing tensor, the leading shape, then each
+    tensor's device before its shape, dtype and contiguity."""
+    terms = int(terms)
+    if len(tensors) != len(table):
+        raise RuntimeError("zest_hip: %s takes %d tensors, got %d" % (who, len(table), len(tensors)))
+    if terms <= 0 or terms & ~all_terms:
+        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
+    for t, row in zip(tensors, table):
+        if t is None and terms & row[2] and (gates is None or gates.get(row[0], True)):
+            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, row[0]))
+    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
+    lead = tuple(int(n) for n in first.shape[:lead_rank])
+    lead_check(who, terms, first, lead)
+    for t, row in zip(tensors, table):
+        if t is None:
+            continue
+        name, want = row[0], lead + ((row[1],) if row[1] else ())
+        if not t.is_cuda:
+            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
+            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
+                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
+    return first, lead, terms
+
+
+def _grad_buffers(who, inputs, want, grads, device):
+    """One gradient buffer per input: None where `want` is false or the input is None, else the given buffer (checked)
+    or a fresh one."""
+    out = []
+    for k, t in enumerate(inputs):
+        g = None
+        if want[k] and t is not None:
+            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
+            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != device:
+                raise RuntimeError("zest_hip: %s gradient buffer %d must be a contiguous fp32 %s on %s"
+                                   % (who, k, tuple(t.shape), device))
+        out.append(g)
+    return out
+
+
+def _totals_row(who, totals, cols, device):
+    if not torch.is_tensor(totals) or tuple(totals.shape) != (cols,) or totals.dtype != torch.float32 \
+            or not totals.is_contiguous() or totals.device != device:
+        raise RuntimeError("zest_hip: %s: totals must be a contiguous fp32 (%d,) on %s" % (who, cols, device))
+
+
 def sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp=1.0, w_st=1.0, want=(True, True, True, True), grads=None):
     """Scene-flow regularisers, one launch: ref / post / prev / pp [R,S,3] NDC points (None where no requested
     term reads the tensor), terms a mask of SF_* -> (loss_ray [R,2]: per-ray parts of the spatial and the temporal
@@ -338,15 +389,7 @@ def sf_reg(ref, post, prev, pp, terms, H, W, focal, w_sp=1.0, w_st=1.0, want=(Tr
                            "for a temporal term; got R=%d S=%d terms=0x%x" % (R, S, terms))
     scale_sp = 1.0 / (3.0 * R * (n95 - 1)) if n95 >= 2 else 0.0
     scale_st = 1.0 / (3.0 * R * n90) if n90 >= 1 else 0.0
-    out = []
-    for k in range(4):
-        g = None
-        if want[k] and pts[k] is not None:
-            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(pts[k])
-            if g.shape != pts[k].shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != ref.device:
-                raise RuntimeError("zest_hip: sf_reg gradient buffer %d must be a contiguous fp32 %s on %s"
-                                   % (k, tuple(pts[k].shape), ref.device))
-        out.append(g)
+    out = _grad_buffers("sf_reg", pts, want, grads, ref.device)
     loss_ray = torch.empty(R, 2, device=ref.device, dtype=torch.float32)
     _check(lib().zest_sf_reg_fwd(_ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]), terms, R, S, n95, n90,
                                  int(H), int(W), float(focal), scale_sp, scale_st, float(w_sp), float(w_st),
@@ -365,41 +408,18 @@ SF_SAMPLE_TENSORS = (("sf_ref2post", 3, SFS_CYCLE | SFS_SF_MIN), ("sf_post2ref",
                      ("weights", 0, SFS_SF_MIN), ("blend", 0, SFS_ENTROPY))
 
 
-def _sf_sample_inputs(who, tensors, terms):
-    """Shape, dtype, device and contiguity of the eight tensors (None where no requested term reads one), checked
-    before the library is touched -> (the tensors as given, R, S, terms)."""
-    terms = int(terms)
-    if len(tensors) != len(SF_SAMPLE_TENSORS):
-        raise RuntimeError("zest_hip: %s takes %d tensors, got %d" % (who, len(SF_SAMPLE_TENSORS), len(tensors)))
-    if terms <= 0 or terms & ~SFS_ALL:
-        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
-    for t, (name, _, readers) in zip(tensors, SF_SAMPLE_TENSORS):
-        if t is None and terms & readers:
-            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
-    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
-    if first.dim() < 2:
+def _sf_sample_lead(who, terms, first, lead):
+    if len(lead) < 2:
         raise RuntimeError("zest_hip: %s needs tensors [R,S] and [R,S,3], got %s" % (who, tuple(first.shape)))
-    R, S = int(first.shape[0]), int(first.shape[1])
-    if R < 1 or S < 1:
-        raise RuntimeError("zest_hip: %s needs R >= 1 and S >= 1, got R=%d S=%d" % (who, R, S))
-    for t, (name, last, _) in zip(tensors, SF_SAMPLE_TENSORS):
-        if t is None:
-            continue
-        want = (R, S, 3) if last else (R, S)
-        if not t.is_cuda:
-            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
-        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
-            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
-                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
-    return R, S, terms
+    if min(lead) < 1:
+        raise RuntimeError("zest_hip: %s needs R >= 1 and S >= 1, got R=%d S=%d" % ((who,) + lead))
 
 
 def sf_sample_fwd(tensors, terms=SFS_ALL):
     """Per-sample terms of the scene-flow training loss, forward launch.  tensors: the eight of SF_SAMPLE_TENSORS,
     contiguous fp32 [R,S,3] / [R,S] (None where no requested term reads one) -> partials [R, SF_SAMPLE_COLS], one row
     of partial sums per ray (include/zest_render.h names the columns)."""
-    R, S, terms = _sf_sample_inputs("sf_sample_fwd", tensors, terms)
-    first = next(t for t in tensors if t is not None)
+    first, (R, S), terms = _term_inputs("sf_sample_fwd", tensors, SF_SAMPLE_TENSORS, terms, SFS_ALL, 2, _sf_sample_lead)
     partials = torch.empty(R, SF_SAMPLE_COLS, device=first.device, dtype=torch.float32)
     _check(lib().zest_sf_sample_fwd(*[_ptr(t) for t in tensors], terms, R, S, _ptr(partials), _stream(first)),
            "zest_sf_sample_fwd")
@@ -410,20 +430,9 @@ def sf_sample_bwd(tensors, totals, terms=SFS_ALL, coeff=(1.0, 1.0, 1.0, 1.0), wa
     """Backward launch: totals [SF_SAMPLE_COLS] = sf_sample_fwd(...).sum(0) (it stays on the device), coeff = (c_cyc, c_prob, c_min, c_ent) -> the gradients of c_cyc cycle + c_prob prob_reg +
     c_min sf_min + c_ent entropy with respect to the eight tensors (None where `want` is false or the tensor is None).
     grads: optional preallocated tensors (or None) to write into; every row of them is written."""
-    R, S, terms = _sf_sample_inputs("sf_sample_bwd", tensors, terms)
-    first = next(t for t in tensors if t is not None)
-    if not torch.is_tensor(totals) or tuple(totals.shape) != (SF_SAMPLE_COLS,) or totals.dtype != torch.float32 \
-            or not totals.is_contiguous() or totals.device != first.device:
-        raise RuntimeError("zest_hip: sf_sample_bwd: totals must be a contiguous fp32 (%d,) on %s" % (SF_SAMPLE_COLS, first.device))
-    out = []
-    for k, t in enumerate(tensors):
-        g = None
-        if want[k] and t is not None:
-            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
-            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
-                raise RuntimeError("zest_hip: sf_sample_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
-                                   % (k, tuple(t.shape), first.device))
-        out.append(g)
+    first, (R, S), terms = _term_inputs("sf_sample_bwd", tensors, SF_SAMPLE_TENSORS, terms, SFS_ALL, 2, _sf_sample_lead)
+    _totals_row("sf_sample_bwd", totals, SF_SAMPLE_COLS, first.device)
+    out = _grad_buffers("sf_sample_bwd", tensors, want, grads, first.device)
     c = [float(v) for v in coeff]
     _check(lib().zest_sf_sample_bwd(*[_ptr(t) for t in tensors], terms, R, S, _ptr(totals), *c,
                                     *[_ptr(g) for g in out], _stream(first)), "zest_sf_sample_bwd")
@@ -445,32 +454,17 @@ SF_RAY_TENSORS = (("target", 3, SFR_PHO | SFR_COMBINED, False), ("rgb_ref", 3, S
 SF_RAY_GRADS = tuple(k for k, t in enumerate(SF_RAY_TENSORS) if t[3])        # positions of the ten that take a gradient
 
 
-def _sf_ray_inputs(who, tensors, terms, late_phase, five_frames):
-    """Shape, dtype, device and contiguity of the seventeen tensors (None where no requested term reads one), checked
-    before the library is touched -> (R, terms)."""
-    terms = int(terms)
-    if len(tensors) != len(SF_RAY_TENSORS):
-        raise RuntimeError("zest_hip: %s takes %d tensors, got %d" % (who, len(SF_RAY_TENSORS), len(tensors)))
-    if terms <= 0 or terms & ~SFR_ALL:
-        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
-    for t, (name, _, readers, _) in zip(tensors, SF_RAY_TENSORS):
-        read = terms & readers and (name != "rgb_pp_dy" or five_frames) and (name != "weights_dd" or late_phase or five_frames)
-        if t is None and read:
-            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
-    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
-    R = int(first.shape[0]) if first.dim() else 0
-    if R < 1:
+def _sf_ray_lead(who, terms, first, lead):
+    if not lead or lead[0] < 1:
         raise RuntimeError("zest_hip: %s needs R >= 1, got %s" % (who, tuple(first.shape)))
-    for t, (name, last, _, _) in zip(tensors, SF_RAY_TENSORS):
-        if t is None:
-            continue
-        want = (R, last) if last else (R,)
-        if not t.is_cuda:
-            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
-        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
-            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
-                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
-    return R, terms
+
+
+def _sf_ray_inputs(who, tensors, terms, late_phase, five_frames):
+    """_term_inputs for the seventeen tensors, two of which the photometric term reads in some phases only
+    -> (first, R, terms)."""
+    gates = {"rgb_pp_dy": bool(five_frames), "weights_dd": bool(late_phase or five_frames)}
+    first, (R,), terms = _term_inputs(who, tensors, SF_RAY_TENSORS, terms, SFR_ALL, 1, _sf_ray_lead, gates)
+    return first, R, terms
 
 
 def sf_ray_fwd(tensors, terms=SFR_ALL, late_phase=False, five_frames=True, coeff=(1.0, 1.0, 1.0, 1.0)):
@@ -478,8 +472,7 @@ def sf_ray_fwd(tensors, terms=SFR_ALL, late_phase=False, five_frames=True, coeff
     contiguous fp32 [R,3] / [R,2] / [R] (None where no requested term reads one) -> result [SF_RAY_COLS]: pho, combined,
     flow, depth, then the sums, medians and scales the backward reads, last c_pho pho + c_comb combined + c_flow flow +
     c_depth depth for coeff = (c_pho, c_comb, c_flow, c_depth) (include/zest_render.h names the columns)."""
-    R, terms = _sf_ray_inputs("sf_ray_fwd", tensors, terms, late_phase, five_frames)
-    first = next(t for t in tensors if t is not None)
+    first, R, terms = _sf_ray_inputs("sf_ray_fwd", tensors, terms, late_phase, five_frames)
     result = torch.empty(SF_RAY_COLS, device=first.device, dtype=torch.float32)
     _check(lib().zest_sf_ray_fwd(*[_ptr(t) for t in tensors], terms, int(bool(late_phase)), int(bool(five_frames)), R,
                                  *[float(v) for v in coeff], _ptr(result), _stream(first)), "zest_sf_ray_fwd")
@@ -492,24 +485,14 @@ def sf_ray_bwd(tensors, totals, terms=SFR_ALL, late_phase=False, five_frames=Tru
     c_depth) -> the gradients of c_pho pho + c_comb combined + c_flow flow + c_depth depth with respect to the ten
     tensors of SF_RAY_GRADS, in that order (None where `want` is false or the tensor is None).  grads: optional
     preallocated tensors (or None) to write into; every row of them is written."""
-    R, terms = _sf_ray_inputs("sf_ray_bwd", tensors, terms, late_phase, five_frames)
-    first = next(t for t in tensors if t is not None)
-    if not torch.is_tensor(totals) or tuple(totals.shape) != (SF_RAY_COLS,) or totals.dtype != torch.float32 \
-            or not totals.is_contiguous() or totals.device != first.device:
-        raise RuntimeError("zest_hip: sf_ray_bwd: totals must be a contiguous fp32 (%d,) on %s" % (SF_RAY_COLS, first.device))
-    out = []
-    for k, i in enumerate(SF_RAY_GRADS):
-        t, g = tensors[i], None
-        if want[k] and t is not None:
-            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
-            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
-                raise RuntimeError("zest_hip: sf_ray_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
-                                   % (k, tuple(t.shape), first.device))
-        out.append(g)
+    first, R, terms = _sf_ray_inputs("sf_ray_bwd", tensors, terms, late_phase, five_frames)
+    _totals_row("sf_ray_bwd", totals, SF_RAY_COLS, first.device)
+    out = _grad_buffers("sf_ray_bwd", [tensors[i] for i in SF_RAY_GRADS], want, grads, first.device)
     c = [float(v) for v in coeff]
     _check(lib().zest_sf_ray_bwd(*[_ptr(t) for t in tensors], terms, int(bool(late_phase)), int(bool(five_frames)), R,
                                  _ptr(totals), *c, *[_ptr(g) for g in out], _stream(first)), "zest_sf_ray_bwd")
     return out
+
 
 PT_MSE, PT_TV, PT_SMOOTH = 1, 2, 4
 PT_ALL = PT_MSE | PT_TV | PT_SMOOTH
@@ -522,41 +505,19 @@ PATCH_FWD_THREADS, PATCH_BWD_THREADS = 1024, 256
 PATCH_TENSORS = (("rgb", 3, PT_MSE | PT_SMOOTH, True), ("target", 3, PT_MSE, False), ("depth", 0, PT_TV | PT_SMOOTH, True))
 
 
-def _patch_inputs(who, rgb, target, depth, terms):
-    """Shape, dtype, device and contiguity of the three tensors (None where no requested term reads one), checked before
-    the library is touched -> (P, H, W, terms)."""
-    terms = int(terms)
-    if terms <= 0 or terms & ~PT_ALL:
-        raise RuntimeError("zest_hip: %s: bad term mask 0x%x" % (who, terms))
-    tensors = (rgb, target, depth)
-    for t, (name, _, readers, _) in zip(tensors, PATCH_TENSORS):
-        if t is None and terms & readers:
-            raise RuntimeError("zest_hip: %s: terms 0x%x read %s, which is None" % (who, terms, name))
-    first = next(t for t in tensors if t is not None)       # every term reads a tensor: there is one
-    lead = tuple(first.shape[:3])
+def _patch_lead(who, terms, first, lead):
     if len(lead) != 3 or min(lead) < 1:
         raise RuntimeError("zest_hip: %s needs [P,H,W(,3)] with P, H, W >= 1, got %s" % (who, tuple(first.shape)))
     if terms & (PT_TV | PT_SMOOTH) and min(lead[1:]) < 2:
         raise RuntimeError("zest_hip: %s: terms 0x%x take neighbour differences, %s leaves a mean over no element"
                            % (who, terms, tuple(first.shape)))
-    for t, (name, last, _, _) in zip(tensors, PATCH_TENSORS):
-        if t is None:
-            continue
-        want = lead + ((last,) if last else ())
-        if not t.is_cuda:
-            raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
-        if tuple(t.shape) != want or t.dtype != torch.float32 or not t.is_contiguous() or t.device != first.device:
-            raise RuntimeError("zest_hip: %s: %s must be a contiguous fp32 %s on %s, got %s %s on %s"
-                               % (who, name, want, first.device, t.dtype, tuple(t.shape), t.device))
-    return lead + (terms,)
 
 
 def patch_terms_fwd(rgb, target, depth, terms=PT_ALL, coeff=(1.0, 1.0, 1.0)):
     """Patch terms of the static training step, forward launch.  rgb, target [P,H,W,3], depth [P,H,W], contiguous fp32
     (None where no requested term reads one) -> result [PATCH_COLS]: mse, tv, smooth, the five sums they come from, last
     c_mse mse + c_tv tv + c_smooth smooth for coeff = (c_mse, c_tv, c_smooth) (include/zest_render.h names the columns)."""
-    P, H, W, terms = _patch_inputs("patch_terms_fwd", rgb, target, depth, terms)
-    first = next(t for t in (rgb, target, depth) if t is not None)
+    first, (P, H, W), terms = _term_inputs("patch_terms_fwd", (rgb, target, depth), PATCH_TENSORS, terms, PT_ALL, 3, _patch_lead)
     result = torch.empty(PATCH_COLS, device=first.device, dtype=torch.float32)
     _check(lib().zest_patch_terms_fwd(_ptr(rgb), _ptr(target), _ptr(depth), terms, P, H, W, *[float(v) for v in coeff],
                                       _ptr(result), _stream(first)), "zest_patch_terms_fwd")
@@ -567,17 +528,8 @@ def patch_terms_bwd(rgb, target, depth, terms=PT_ALL, coeff=(1.0, 1.0, 1.0), wan
     """Backward launch -> (d_rgb, d_depth), the gradients of c_mse mse + c_tv tv + c_smooth smooth (None where `want`
     is false or the tensor is None; zeros where no requested term reads the tensor).  grads: optional preallocated
     tensors (or None) to write into; every element of them is written."""
-    P, H, W, terms = _patch_inputs("patch_terms_bwd", rgb, target, depth, terms)
-    first = next(t for t in (rgb, target, depth) if t is not None)
-    out = []
-    for k, t in enumerate((rgb, depth)):
-        g = None
-        if want[k] and t is not None:
-            g = grads[k] if grads is not None and grads[k] is not None else torch.empty_like(t)
-            if g.shape != t.shape or g.dtype != torch.float32 or not g.is_contiguous() or g.device != first.device:
-                raise RuntimeError("zest_hip: patch_terms_bwd gradient buffer %d must be a contiguous fp32 %s on %s"
-                                   % (k, tuple(t.shape), first.device))
-        out.append(g)
+    first, (P, H, W), terms = _term_inputs("patch_terms_bwd", (rgb, target, depth), PATCH_TENSORS, terms, PT_ALL, 3, _patch_lead)
+    out = _grad_buffers("patch_terms_bwd", (rgb, depth), want, grads, first.device)
     _check(lib().zest_patch_terms_bwd(_ptr(rgb), _ptr(target), _ptr(depth), terms, P, H, W, *[float(v) for v in coeff],
                                       _ptr(out[0]), _ptr(out[1]), _stream(first)), "zest_patch_terms_bwd")
     return out

@@ -52,31 +52,52 @@ def distortion_loss(ray_weights, t_vals):
     return zest_autograd.DistortionFn.apply(ray_weights[0], t.detach())
 
 
-def _sf_points(who, named, spatial, temporal):
-    """Check the point tensors of a scene-flow term BEFORE the library is touched and flatten them to
-    contiguous fp32 [R,S,3].  named: [(argument name, tensor)], all of one shape [..., S, 3]."""
-    first_name, first = named[0]
-    for name, t in named:
-        if not torch.is_tensor(t) or t.dim() < 2 or t.shape[-1] != 3:
-            raise RuntimeError("%s: %s must be a tensor [..., N_samples, 3], got %s"
-                               % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-        if t.shape != first.shape:
-            raise RuntimeError("%s: %s %s does not match %s %s"
-                               % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
-    S = first.shape[-2]
+def _check_shapes(who, named, min_lead, text, exact=False):
+    """The shape pass every loss here makes BEFORE the library is touched.  named: [(argument name, tensor, trailing
+    extent or 0)]; a tensor is [lead..., trailing extent] with at least (exact: exactly)
+    min_lead leading extents, which agree with the first tensor's; `text` names them in the refusal.  Last, the empty
+    batch.  The caller's own refusals come next, then _check_devices: a tensor too small for its loss is refused as
+    that, wherever it lives."""
+    first_name, first, _ = named[0]
+    first_lead = None
+    for name, t, last in named:
+        rank = min_lead + (1 if last else 0)
+        if not torch.is_tensor(t) or (t.dim() != rank if exact else t.dim() < rank) or (last and t.shape[-1] != last):
+            raise RuntimeError("%s: %s must be a tensor %s%s], got %s"
+                               % (who, name, text, ", %d" % last if last else "",
+                                  tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        lead = t.shape[:-1] if last else t.shape
+        if first_lead is None:
+            first_lead = lead
+        if lead != first_lead:
+            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
     if first.numel() == 0:
         raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
+
+
+def _check_devices(who, named):
+    """The device pass, after every refusal of a shape: all on one HIP device."""
+    first_name, first, _ = named[0]
+    for name, t, _ in named:
+        if not t.is_cuda:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if t.device != first.device:
+            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
+
+
+def _sf_points(who, named, spatial, temporal):
+    """Check the point tensors of a scene-flow term and flatten them to contiguous fp32 [R,S,3].  named: [(argument
+    name, tensor)], all of one shape [..., S, 3]."""
+    named = [(name, t, 3) for name, t in named]
+    _check_shapes(who, named, 1, "[..., N_samples")
+    S = named[0][1].shape[-2]
     if spatial and int(S * 0.95) < 2:
         raise RuntimeError("%s: %d samples per ray leave int(%d * 0.95) = %d < 2 for the neighbour difference"
                            % (who, S, S, int(S * 0.95)))
     if temporal and int(S * 0.9) < 1:
         raise RuntimeError("%s: %d samples per ray leave int(%d * 0.9) = 0 samples" % (who, S, S))
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
-        if t.device != first.device:
-            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
-    return [t.contiguous().float().reshape(-1, S, 3) for _, t in named]
+    _check_devices(who, named)
+    return [t.contiguous().float().reshape(-1, S, 3) for _, t, _ in named]
 
 
 def compute_sf_smooth_loss(pts_1_ndc, pts_2_ndc, H, W, f):
@@ -115,28 +136,6 @@ def scene_flow_regularisers(raw_pts_ref, raw_pts_post, raw_pts_prev, raw_pts_pp,
     return zest_autograd.SceneFlowRegFn.apply(*pts, terms, H, W, f, float(w_sp), float(w_st))
 
 
-def _sf_samples(who, named):
-    """Check the eight tensors of the per-sample terms BEFORE the library is touched and flatten them to contiguous
-    fp32 [R,S,3] / [R,S].  named: [(argument name, tensor, trailing extent or 0)]; the leading dimensions and S agree."""
-    first_name, first, _ = named[0]
-    for name, t, last in named:
-        if not torch.is_tensor(t) or t.dim() < (3 if last else 2) or (last and t.shape[-1] != last):
-            raise RuntimeError("%s: %s must be a tensor [..., N_samples%s], got %s"
-                               % (who, name, ", 3" if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-        lead = t.shape[:-1] if last else t.shape
-        if lead != first.shape[:-1]:
-            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
-    if first.numel() == 0:
-        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
-    for name, t, _ in named:
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
-        if t.device != first.device:
-            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
-    S = first.shape[-2]
-    return [t.contiguous().float().reshape(-1, S, 3) if last else t.contiguous().float().reshape(-1, S) for _, t, last in named]
-
-
 def scene_flow_sample_terms(raw_sf_ref2post, raw_sf_post2ref, raw_sf_ref2prev, raw_sf_prev2ref, raw_prob_ref2post,
                             raw_prob_ref2prev, weights_ref_dy, raw_blend_w, w_cyc=1.0, w_prob=1.0, w_min=1.0, w_entropy=1.0):
     """The per-sample terms of one scene-flow training step, values and gradients from two launches:
@@ -150,37 +149,12 @@ def scene_flow_sample_terms(raw_sf_ref2post, raw_sf_post2ref, raw_sf_ref2prev, r
              ("raw_sf_ref2prev", raw_sf_ref2prev, 3), ("raw_sf_prev2ref", raw_sf_prev2ref, 3),
              ("raw_prob_ref2post", raw_prob_ref2post, 0), ("raw_prob_ref2prev", raw_prob_ref2prev, 0),
              ("weights_ref_dy", weights_ref_dy, 0), ("raw_blend_w", raw_blend_w, 0)]
-    flat = _sf_samples("scene_flow_sample_terms", named)
+    _check_shapes("scene_flow_sample_terms", named, 2, "[..., N_samples")
+    _check_devices("scene_flow_sample_terms", named)
+    S = raw_sf_ref2post.shape[-2]
+    flat = [t.contiguous().float().reshape(-1, S, 3) if last else t.contiguous().float().reshape(-1, S) for _, t, last in named]
     return zest_autograd.SceneFlowSampleFn.apply(*flat, zest_hip.SFS_ALL, float(w_cyc), float(w_prob), float(w_min),
                                                  float(w_entropy))
-
-
-def _sf_rays(who, named, with_depth):
-    """Check the tensors of the per-ray terms BEFORE the library is touched and flatten them to contiguous fp32 [R,3] /
-    [R,2] / [R].  named: [(argument name, tensor or None, trailing extent or 0)]; the first is there and the leading
-    dimensions agree.  Shapes first, then the batch (empty; a single ray under the whitened depths), then the device."""
-    first_name, first, _ = named[0]
-    given = [(name, t, last) for name, t, last in named if t is not None]
-    for name, t, last in given:
-        if not torch.is_tensor(t) or t.dim() < (1 if last else 0) or (last and t.shape[-1] != last):
-            raise RuntimeError("%s: %s must be a tensor [...%s], got %s"
-                               % (who, name, ", %d" % last if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-    lead = first.shape[:-1]
-    for name, t, last in given:
-        if (t.shape[:-1] if last else t.shape) != lead:
-            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
-    if first.numel() == 0:
-        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
-    if with_depth and first.numel() == first.shape[-1]:
-        raise RuntimeError("%s: one ray %s: its depth is its own median, the whitened depth prior is 0 / 0"
-                           % (who, tuple(first.shape)))
-    for name, t, _ in given:
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
-        if t.device != first.device:
-            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
-    return [None if t is None else t.contiguous().float().reshape(-1, last) if last else t.contiguous().float().reshape(-1)
-            for _, t, last in named]
 
 
 def scene_flow_ray_terms(target_s, rgb_map_ref, rgb_map_ref_dy, rgb_map_post_dy, rgb_map_prev_dy, rgb_map_pp_dy,
@@ -218,7 +192,14 @@ def scene_flow_ray_terms(target_s, rgb_map_ref, rgb_map_ref_dy, rgb_map_post_dy,
     for flow, gt, mask in ((flow_fwd, rays_flow_fwd_gt, rays_mask_fwd_gt), (flow_bwd, rays_flow_bwd_gt, rays_mask_bwd_gt)):
         if flow is not None and (gt is None or mask is None):
             raise RuntimeError("%s: a rendered flow is given without its ground truth or its mask" % who)
-    flat = _sf_rays(who, named, True)
+    given = [n for n in named if n[1] is not None]
+    _check_shapes(who, given, 0, "[...")
+    if target_s.numel() == target_s.shape[-1]:
+        raise RuntimeError("%s: one ray %s: its depth is its own median, the whitened depth prior is 0 / 0"
+                           % (who, tuple(target_s.shape)))
+    _check_devices(who, given)
+    flat = [None if t is None else t.contiguous().float().reshape(-1, last) if last else t.contiguous().float().reshape(-1)
+            for _, t, last in named]
     flat[8] = flat[8].detach()                                  # weights_map_dd carries no gradient (train.py:396)
     terms = zest_hip.SFR_PHO | zest_hip.SFR_COMBINED | zest_hip.SFR_DEPTH
     terms |= (zest_hip.SFR_FLOW_FWD if flow_fwd is not None else 0) | (zest_hip.SFR_FLOW_BWD if flow_bwd is not None else 0)
@@ -242,6 +223,11 @@ def _whitened_depth_loss(pred, gt):
     return ((whiten(pred) - whiten(gt)) ** 2).mean()
 
 
+def _hparams(hparams):
+    """name -> value, of hparams given as a dict or as attributes."""
+    return hparams.__getitem__ if isinstance(hparams, dict) else lambda name: getattr(hparams, name)
+
+
 def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_frames, hparams, global_step,
                        decay_iteration, loss=None, ray_terms="hip"):
     """The loss of one scene-flow training step: MVSNeRFSystem.train_sf_step (train.py:346-585) without its class.
@@ -252,11 +238,7 @@ def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_fr
     ray_terms: "hip" evaluates the per-ray terms in scene_flow_ray_terms, "torch" as a torch composition (so does any
     `loss` that is not a mean-reduced nn.MSELoss: the kernel knows that criterion only).
     -> (sceneflow_loss with the graph, {name: logged value}) with the reference's ten names, weighted as it logs them."""
-    if isinstance(hparams, dict):
-        hp = hparams.__getitem__
-    else:
-        def hp(name):
-            return getattr(hparams, name)
+    hp = _hparams(hparams)
     if ray_terms not in ("hip", "torch"):
         raise RuntimeError("train_sf_step_loss: ray_terms must be 'hip' or 'torch', got %r" % (ray_terms,))
     if loss is None:
@@ -338,26 +320,14 @@ def train_sf_step_loss(results, images_shape, focal, fnb_w2cs, frame_t, total_fr
 
 
 def _patches(who, named):
-    """Check the patch tensors BEFORE the library is touched and return them as contiguous fp32.  named: [(argument
-    name, tensor [B,H,W] or [B,H,W,last], last or 0)]; B, H and W agree.  Shapes first, then the batch (empty; too small
-    for a neighbour difference), then the device."""
-    first_name, first, _ = named[0]
-    for name, t, last in named:
-        if not torch.is_tensor(t) or t.dim() != (4 if last else 3) or (last and t.shape[-1] != last):
-            raise RuntimeError("%s: %s must be a tensor [B, H, W%s], got %s"
-                               % (who, name, ", %d" % last if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-        if t.shape[:3] != first.shape[:3]:
-            raise RuntimeError("%s: %s %s does not match %s %s" % (who, name, tuple(t.shape), first_name, tuple(first.shape)))
-    if first.numel() == 0:
-        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(first.shape)))
-    if min(first.shape[1:3]) < 2:
+    """Check the patch tensors and return them as contiguous fp32.  named: [(argument name, tensor [B,H,W] or
+    [B,H,W,last], last or 0)]; B, H and W agree."""
+    _check_shapes(who, named, 3, "[B, H, W", exact=True)
+    H, W = named[0][1].shape[1:3]
+    if min(H, W) < 2:
         raise RuntimeError("%s: patches of %d x %d leave no neighbour difference in one direction (the mean over no "
-                           "element is undefined)" % (who, first.shape[1], first.shape[2]))
-    for name, t, _ in named:
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
-        if t.device != first.device:
-            raise RuntimeError("%s: %s is on %s, %s on %s" % (who, name, t.device, first_name, first.device))
+                           "element is undefined)" % (who, H, W))
+    _check_devices(who, named)
     return [t.contiguous().float() for _, t, _ in named]
 
 
@@ -393,27 +363,15 @@ def patch_terms(rgb_pred, rgb_gt, depth_pred, patch_size, w_rec=1.0, w_tv=0.0, w
 
 
 def _patch_terms(who, rgb_pred, rgb_gt, depth_pred, patch_size, terms, w_rec, w_tv, w_smooth):
-    """patch_terms with the term mask given (a term may be in it with the weight 0: evaluated, not part of the total).
-    Shapes first, then the batch and the patch size, then the device: all BEFORE the library is touched."""
+    """patch_terms with the term mask given (a term may be in it with the weight 0: evaluated, not part of the total)."""
     named = [("rgb_pred", rgb_pred, 3), ("rgb_gt", rgb_gt, 3), ("depth_pred", depth_pred, 0)]
-    for name, t, last in named:
-        if not torch.is_tensor(t) or t.dim() < (2 if last else 1) or (last and t.shape[-1] != last):
-            raise RuntimeError("%s: %s must be a tensor [..., N_rays%s], got %s"
-                               % (who, name, ", 3" if last else "", tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
-        if (t.shape[:-1] if last else t.shape) != rgb_pred.shape[:-1]:
-            raise RuntimeError("%s: %s %s does not match rgb_pred %s" % (who, name, tuple(t.shape), tuple(rgb_pred.shape)))
-    if rgb_pred.numel() == 0:
-        raise RuntimeError("%s: empty batch %s (the mean over no element is undefined)" % (who, tuple(rgb_pred.shape)))
+    _check_shapes(who, named, 1, "[..., N_rays")
     ps = int(patch_size)
     if ps < 2:
         raise RuntimeError("%s: patch_size %d < 2 leaves no neighbour difference" % (who, ps))
     if rgb_pred.shape[-2] % (ps * ps):
         raise RuntimeError("%s: %d rays are not a multiple of patch_size^2 = %d" % (who, rgb_pred.shape[-2], ps * ps))
-    for name, t, _ in named:
-        if not t.is_cuda:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
-        if t.device != rgb_pred.device:
-            raise RuntimeError("%s: %s is on %s, rgb_pred on %s" % (who, name, t.device, rgb_pred.device))
+    _check_devices(who, named)
     rgb = rgb_pred.contiguous().float().reshape(-1, ps, ps, 3) if terms & (zest_hip.PT_MSE | zest_hip.PT_SMOOTH) else None
     gt = rgb_gt.detach().contiguous().float().reshape(-1, ps, ps, 3) if terms & zest_hip.PT_MSE else None
     depth = depth_pred.contiguous().float().reshape(-1, ps, ps) if terms & (zest_hip.PT_TV | zest_hip.PT_SMOOTH) else None
@@ -441,11 +399,7 @@ def train_step_loss(results, hparams, adversarial=False):
     -> (loss with the graph, {name: logged value}) with the reference's names, weighted as it logs them: tv_depth_loss,
     depth_smooth_loss, distortion_loss (each where its flag is set), G_rec_loss (adversarial only) and train_PSNR =
     10 log10(1 / mse)."""
-    if isinstance(hparams, dict):
-        hp = hparams.__getitem__
-    else:
-        def hp(name):
-            return getattr(hparams, name)
+    hp = _hparams(hparams)
     if hp("train_sceneflow"):
         raise RuntimeError("train_step_loss: hparams.train_sceneflow is set: that step's loss is train_sf_step_loss")
     l_reg = float(hp("lambda_depth_reg")) if hp("with_depth_loss_reg") else 0.0

@@ -138,8 +138,9 @@ class MlpSpec:
         return 5 if self.static else 12
 
 
-def mlp_forward(state, x, spec, prefix="nerf."):
-    """x [M, in_ch] -> [M, out_ch] = (rgb raw, sigma raw, extras).
+def mlp_forward(state, x, spec, prefix="nerf.", relu=torch.relu):
+    """x [M, in_ch] -> [M, out_ch] = (rgb raw, sigma raw, extras).  relu: the callable applied wherever the network has a
+    ReLU (a test can pass one that also records its inputs).
 
     v0 restates Renderer.forward (/root/reference/networks.py:150-221): trunk layers
     ``relu(Linear(h) * m)`` with m = pts_bias(feats) when use_mvs, skip re-concat
@@ -162,7 +163,7 @@ def mlp_forward(state, x, spec, prefix="nerf."):
         h = lin("pts_linears.%d" % i, h)
         if m is not None:
             h = h * m if spec.net_type == "v0" else h + m
-        h = torch.relu(h)
+        h = relu(h)
         if i in spec.skips:
             h = torch.cat([pts, h], -1)
     extras = []
@@ -173,9 +174,9 @@ def mlp_forward(state, x, spec, prefix="nerf."):
             extras = [torch.tanh(lin("sf_linear", h)), torch.sigmoid(lin("prob_linear", h))]
     alpha = lin("alpha_linear", h)
     if spec.net_type == "v2":
-        alpha = torch.relu(alpha)
+        alpha = relu(alpha)
     g = torch.cat([lin("feature_linear", h), views], -1)
-    g = torch.relu(lin("views_linears.0", g))
+    g = relu(lin("views_linears.0", g))
     rgb = lin("rgb_linear", g)
     if spec.net_type == "v2":
         rgb = torch.sigmoid(rgb)

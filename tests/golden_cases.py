@@ -116,8 +116,11 @@ def mlp_inputs(seed, variant, M=64):
 
 # --------------------------------------------------------------- loss-side cases
 def loss_inputs(seed, R=12, S=40, jitter=False):
-    """Compositing-like weights, sorted normalised sample positions, NDC points around the
-    frustum (some beyond the clamp of NDC2Euclidean) and a neighbour camera."""
+    """Compositing-like weights (a ray's sum in [0.3, 1]), sorted normalised sample positions, NDC points around
+    the frustum and a neighbour camera.  The samples' z spans [-1.2, 1.05], beyond the clamp of NDC2Euclidean
+    ([-1, 0.99]) at both ends, but projection_from_ndc clamps the EXPECTED point of a ray, whose z is a weighted mean
+    of about S such draws and stays well inside (for the case loss_side in [-0.23, 0.08]): these inputs never engage
+    the clamp.  grad_edge_cases.project_case moves whole rays beyond it."""
     g = zs.rng(seed)
     w = g.uniform(0, 1, size=(1, R, S)).astype(np.float32)
     w = (w / w.sum(-1, keepdims=True) * g.uniform(0.3, 1.0, size=(1, R, 1))).astype(np.float32)

@@ -398,6 +398,38 @@ int zest_patch_terms_bwd(const float *rgb, const float *target, const float *dep
                          int W, float c_mse, float c_tv, float c_smooth, float *d_rgb, float *d_depth,
                          void *stream);
 
+/* GRAF patch discriminator (reference networks.py:845-929): spectrally normalised 4x4 stride-2
+ * convolutions without bias, instance norm (biased variance, eps 1e-5, no affine) and leaky ReLU
+ * (0.2), then a 4x4 convolution of the 4 x 4 map to one logit per patch.  imsize 32, 64 or 128; ndf a
+ * multiple of 16 (of 32 for imsize 128), at most 256.  Layers (cin -> cout), in the reference's order:
+ *   imsize  32: 3 -> 2 ndf (norm), 2 ndf -> 4 ndf (norm), 4 ndf -> 8 ndf (norm), 8 ndf -> 1
+ *   imsize  64: 3 -> ndf, ndf -> 2 ndf (norm), ... as above
+ *   imsize 128: 3 -> ndf/2, ndf/2 -> ndf (norm), ndf -> 2 ndf (norm), ... as above
+ * x: the patches [B,imsize,imsize,3], contiguous fp32.  w, u, v: one device pointer per layer, 16-byte
+ * aligned: weight_orig [cout][cin][4][4], weight_u [cout], weight_v [16 cin] of
+ * torch.nn.utils.spectral_norm.  All arithmetic is fp32 (fp32 MFMA, exact products); no float atomics:
+ * two calls from the same state are bit-identical.
+ * zest_disc_layout: out[0..2] = floats of `saved`, of the forward's and of the backward's `work`;
+ *   out[3] = the number of layers n; out[8 + 8 l ..] per layer: cin, cout, output side, and the offsets
+ *   in `saved` of u [cout], v [16 cin], sigma [1], the raw output [B,side,side,cout] (not for the last
+ *   layer) and its (mean, 1/deviation) table [B,cout,2] (-1 without a norm).  out holds
+ *   8 + 8 ZEST_DISC_MAX_LAYERS entries.
+ * zest_disc_fwd: training != 0 runs one power iteration first, v <- normalize(W^T u),
+ *   u <- normalize(W v) with x / max(|x|, 1e-12), and moves u and v IN PLACE; training == 0 takes them
+ *   as they are.  sigma = u . (W v); the convolutions use W / sigma.  `saved` keeps what a backward of
+ *   THIS forward needs (the u, v and sigma it used, raw outputs, norm constants); logits [B].
+ * zest_disc_bwd: g_logits [B] -> g_x [B,imsize,imsize,3] where not NULL, and g_w (one pointer per
+ *   layer, as w) where not NULL: d/d weight_orig = (G - <G, W/sigma> u v^T) / sigma with u, v constants.
+ *   A NULL g_x skips the first layer's data gradient, a NULL g_w every weight-gradient launch; one of
+ *   the two must be given.  Every element of a given gradient is written once.
+ * Errors: the shapes above; B < 1; NULL or misaligned pointers. */
+#define ZEST_DISC_MAX_LAYERS 6
+int zest_disc_layout(int B, int imsize, int ndf, long long *out);
+int zest_disc_fwd(const float *x, int B, int imsize, int ndf, const float *const *w, float *const *u,
+                  float *const *v, int training, float *saved, float *work, float *logits, void *stream);
+int zest_disc_bwd(const float *x, int B, int imsize, int ndf, const float *const *w, const float *saved,
+                  const float *g_logits, float *work, float *g_x, float *const *g_w, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

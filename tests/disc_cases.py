@@ -1,0 +1,229 @@
+"""Inputs, fixtures and a torch restatement of the GRAF patch discriminator in the static ("svs") training step (the
+reference's networks.GRAFDiscriminator, networks.py:845-929, in MVSNeRFSystem.training_step: the generator's adversarial
+term, train.py:646-654, and the discriminator step, train.py:698-719), shared by tools/gen_golden_disc.py, the CPU and GPU
+tests and tools/bench_disc.py.
+
+Inputs (`state`, `patches`): weight_orig uniform in +-1/sqrt(fan in) (the range of torch's Conv2d initialisation), unit
+u and v, B patches of imsize x imsize colours in (0, 1) as rays [1, B imsize^2, 3], a `fake` and a `real` set.
+
+Restatement (`Composition`): spectral_norm(Conv2d), InstanceNorm2d and LeakyReLU composed as the reference composes them,
+under the reference's state-dict keys; usable in float64 on the CPU (the tests' yardstick) and in fp32 on the device (the
+benchmark's torch leg).  `run_steps` walks the two steps on any module of that interface - the restatement, or the
+reference's own class in tools/gen_golden_disc.py - and returns what the fixtures hold.
+
+The leaky-ReLU kink (`margins`): a pre-activation that lands on the other side of 0 in another summation order changes
+one gradient factor from 1 to 0.2, so gradients can be compared per element only where no pre-activation is that close
+to 0.  For a case compared per element `inputs` measures, on the host, how far the restatement's fp32 pre-activations
+sit from its float64 ones (per layer, the largest deviation) and asserts that every leaky-ReLU input of the float64
+evaluation is at least MARGIN = 10 times that far from 0 - 10 because another summation order moves a value by about
+as much again as fp32 itself does.  SEEDS records, per case, a seed found to satisfy it (tools/gen_golden_disc.py
+--seeds searches).  The production shape (ndf 64 at imsize 64: no seed keeps clear) is compared by norms instead.
+"""
+import functools
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MARGIN = 10.0
+INDICES = {32: (0, 3, 6, 9), 64: (0, 2, 5, 8, 11), 128: (0, 2, 5, 8, 11, 14)}
+# (B, imsize, ndf) of the fixtures tests/golden/disc_<B>x<imsize>_ndf<ndf>.npz; the last is the production shape, whose
+# weight gradients are kept as digests (norm and inner products with N_DIRS seeded directions)
+CASES = ((2, 32, 16), (1, 64, 16), (1, 64, 64))
+DIGEST_CASES = ((1, 64, 64),)
+N_DIRS = 4
+# (B, imsize, ndf) of the restatement tests: per-sample statistics and batch offsets (B = 1, 2, 3 at imsize 32); the
+# layer without a norm (imsize 64); the extra layer and ndf / 2 (imsize 128); channel counts that are multiples of 16
+# but not of 32 or 64 (ndf 48)
+SIZES = ((1, 32, 16), (2, 32, 16), (3, 32, 16), (1, 64, 16), (1, 128, 32), (1, 32, 48))
+# seed per (B, imsize, ndf) for which `margins` >= MARGIN (searched on the CPU)
+# with room to spare: the fp32 deviation is measured with the host's torch, whose summation order differs between hosts.
+# Margins where they were searched: 61, 33, 15 (the best of 1500 seeds: 131 k pre-activations), 50, 41, 45
+SEEDS = {(1, 32, 16): 0, (1, 64, 16): 27, (1, 128, 32): 738, (2, 32, 16): 0, (1, 32, 48): 99, (3, 32, 16): 2}
+DEFAULT_SEED = 0
+
+
+def channels(imsize, ndf):
+    return {32: (3, 2 * ndf), 64: (3, ndf, 2 * ndf), 128: (3, ndf // 2, ndf, 2 * ndf)}[imsize] + (4 * ndf, 8 * ndf, 1)
+
+
+def normed(imsize):
+    """Per strided layer: is it followed by an instance norm."""
+    return {32: (1, 1, 1), 64: (0, 1, 1, 1), 128: (0, 1, 1, 1, 1)}[imsize]
+
+
+def seed_of(B, imsize, ndf):
+    return SEEDS.get((B, imsize, ndf), DEFAULT_SEED)
+
+
+def state(imsize, ndf, seed):
+    """-> {state-dict key: float32 array}, drawn from default_rng((seed, imsize, ndf)) layer by layer: weight_orig, u, v."""
+    rng = np.random.default_rng((seed, imsize, ndf))
+    ch, out = channels(imsize, ndf), {}
+    for i, cin, cout in zip(INDICES[imsize], ch[:-1], ch[1:]):
+        bound = 1.0 / np.sqrt(16.0 * cin)
+        u, v = rng.standard_normal(cout), rng.standard_normal(16 * cin)
+        out["main.%d.weight_orig" % i] = rng.uniform(-bound, bound, (cout, cin, 4, 4))
+        out["main.%d.weight_u" % i] = u / np.linalg.norm(u)
+        out["main.%d.weight_v" % i] = v / np.linalg.norm(v)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def patches(B, imsize, seed, constant=False):
+    """-> {fake, real}: float32 [1, B imsize^2, 3] in (0, 1).  constant: every pixel of a fake patch has the patch's colour."""
+    rng = np.random.default_rng((seed, B, imsize, 77))
+    fake, real = rng.uniform(0.0, 1.0, (2, 1, B * imsize * imsize, 3))
+    if constant:
+        fake = np.repeat(rng.uniform(0.2, 0.8, (1, B, 1, 3)), imsize * imsize, 2).reshape(1, -1, 3)
+    return {"fake": np.ascontiguousarray(fake, dtype=np.float32), "real": np.ascontiguousarray(real, dtype=np.float32)}
+
+
+class Composition(nn.Module):
+    """The discriminator as a composition of torch modules, under the reference's state-dict keys."""
+
+    def __init__(self, nc=3, ndf=64, imsize=64):
+        super().__init__()
+        self.nc, self.ndf, self.imsize = nc, ndf, imsize
+        ch, blocks = channels(imsize, ndf), []
+        for cin, cout, norm in zip(ch[:-2], ch[1:-1], normed(imsize)):
+            blocks.append(nn.utils.spectral_norm(nn.Conv2d(cin, cout, 4, 2, 1, bias=False)))
+            if norm:
+                blocks.append(nn.InstanceNorm2d(cout))
+            blocks.append(nn.LeakyReLU(0.2))
+        blocks.append(nn.utils.spectral_norm(nn.Conv2d(ch[-2], 1, 4, 1, 0, bias=False)))
+        self.main = nn.Sequential(*blocks)
+
+    def forward(self, input):
+        x = input[..., :self.nc].reshape(-1, self.imsize, self.imsize, self.nc).permute(0, 3, 1, 2)
+        return self.main(x)
+
+
+def load(model, st, dtype=torch.float32, device="cpu"):
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()}, strict=True)
+    return model.to(device=device, dtype=dtype)
+
+
+def composition(imsize, ndf, seed, dtype=torch.float64, device="cpu"):
+    return load(Composition(3, ndf, imsize), state(imsize, ndf, seed), dtype, device).train()
+
+
+def uv(model, imsize):
+    """-> {u<i>, v<i>: array} of the module's spectral-norm buffers as they stand."""
+    sd = model.state_dict()
+    out = {}
+    for i in INDICES[imsize]:
+        out["u%d" % i] = sd["main.%d.weight_u" % i].detach().cpu().double().numpy().copy()
+        out["v%d" % i] = sd["main.%d.weight_v" % i].detach().cpu().double().numpy().copy()
+    return out
+
+
+def directions(imsize, ndf, i, shape):
+    """The N_DIRS seeded directions of the weight-gradient digest of layer <i>."""
+    return np.random.default_rng((imsize, ndf, i, 5)).standard_normal((N_DIRS,) + tuple(shape))
+
+
+def digest(g, imsize, ndf, i):
+    g = np.asarray(g, np.float64)
+    return np.linalg.norm(g), np.tensordot(directions(imsize, ndf, i, g.shape), g, g.ndim)
+
+
+def run_steps(make, B, imsize, ndf, seed, lambda_adv=1.0, digests=False, as_tensor=None):
+    """The two steps on a module in training mode, each from the seeded state: make() -> a fresh module with that state
+    (any dtype / device; as_tensor(array) -> its input tensors, default float tensors of the module's dtype on the CPU).
+      generator (train.py:646-652): weights frozen, G_fake_loss = lambda_adv mean (D(fake) - 1)^2, gradient to the image;
+      discriminator (train.py:698-719): detached inputs, fake first, (mean D(fake)^2 + mean (D(real) - 1)^2) / 2, one
+      backward, gradients to every weight_orig.
+    -> {name: float64 array}: gen__logits, gen__G_fake_loss, gen__grad__rgb, gen__u<i>, gen__v<i>; disc__logits_fake,
+    disc__logits_real, disc__D_fake_loss, disc__D_real_loss, disc__total, disc__fake__u<i>, disc__fake__v<i>,
+    disc__real__u<i>, disc__real__v<i> (after that forward), disc__grad__<i> - or, digests, disc__grad_norm__<i> and
+    disc__grad_dots__<i> [N_DIRS]."""
+    inp = patches(B, imsize, seed)
+    out = {}
+    num = lambda t: t.detach().cpu().double().numpy().copy()                 # noqa: E731
+
+    D = make()
+    if as_tensor is None:
+        dt = next(D.parameters()).dtype
+        as_tensor = lambda a: torch.from_numpy(a).to(dt)                    # noqa: E731
+    for prm in D.parameters():
+        prm.requires_grad_(False)
+    rgb = as_tensor(inp["fake"]).requires_grad_(True)
+    pred = D(rgb)
+    loss = lambda_adv * ((pred - 1.0) ** 2).mean()
+    loss.backward()
+    out["gen__logits"], out["gen__G_fake_loss"], out["gen__grad__rgb"] = num(pred).reshape(-1), num(loss), num(rgb.grad)
+    out.update({"gen__" + k: v for k, v in uv(D, imsize).items()})
+
+    D = make()
+    fake, real = as_tensor(inp["fake"]).requires_grad_(True), as_tensor(inp["real"])
+    p_fake = D(fake.detach())
+    out.update({"disc__fake__" + k: v for k, v in uv(D, imsize).items()})
+    d_fake = (p_fake ** 2).mean()
+    p_real = D(real.detach())
+    out.update({"disc__real__" + k: v for k, v in uv(D, imsize).items()})
+    d_real = ((p_real - 1.0) ** 2).mean()
+    total = (d_fake + d_real) / 2
+    total.backward()
+    out["disc__logits_fake"], out["disc__logits_real"] = num(p_fake).reshape(-1), num(p_real).reshape(-1)
+    out["disc__D_fake_loss"], out["disc__D_real_loss"], out["disc__total"] = num(d_fake), num(d_real), num(total)
+    params = dict(D.named_parameters())
+    for i in INDICES[imsize]:
+        g = num(params["main.%d.weight_orig" % i].grad)
+        if digests:
+            out["disc__grad_norm__%d" % i], out["disc__grad_dots__%d" % i] = digest(g, imsize, ndf, i)
+        else:
+            out["disc__grad__%d" % i] = g
+    return out
+
+
+def _preacts(model, xs):
+    """Every leaky-ReLU input of the training-mode forwards of xs, in turn -> [array per (forward, layer)]."""
+    got, hooks = [], []
+    for m in model.main:
+        if isinstance(m, nn.LeakyReLU):
+            hooks.append(m.register_forward_pre_hook(lambda mod, args: got.append(args[0].detach().double().numpy().copy())))
+    with torch.no_grad():
+        for x in xs:
+            model(x)
+    for h in hooks:
+        h.remove()
+    return got
+
+
+def margins(B, imsize, ndf, seed, constant=False):
+    """-> min over the forwards (fake, then real, training mode from the seeded state) and layers of
+    min |pre-activation in float64| / max |its fp32 evaluation - the float64 one|."""
+    inp = patches(B, imsize, seed, constant)
+    pre = {}
+    for dt in (torch.float64, torch.float32):
+        pre[dt] = _preacts(composition(imsize, ndf, seed, dt), [torch.from_numpy(inp[k]).to(dt) for k in ("fake", "real")])
+    return min(float(np.abs(a).min() / max(np.abs(a - b).max(), 1e-300)) for a, b in zip(pre[torch.float64], pre[torch.float32]))
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(B, imsize, ndf, seed=None):
+    """-> (seed, state, patches) of a case that is compared per element; the kink margin is asserted here, on the host."""
+    seed = seed_of(B, imsize, ndf) if seed is None else seed
+    m = margins(B, imsize, ndf, seed)
+    assert m >= MARGIN, ((B, imsize, ndf, seed), m)
+    return seed, state(imsize, ndf, seed), patches(B, imsize, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def restated(B, imsize, ndf, seed=None):
+    """run_steps of the float64 restatement, computed once and shared; do not modify."""
+    seed = seed_of(B, imsize, ndf) if seed is None else seed
+    return run_steps(lambda: composition(imsize, ndf, seed), B, imsize, ndf, seed, digests=(B, imsize, ndf) in DIGEST_CASES)
+
+
+def fixture_path(B, imsize, ndf):
+    return os.path.join(GOLDEN_DIR, "disc_%dx%d_ndf%d.npz" % (B, imsize, ndf))
+
+
+def load_fixture(B, imsize, ndf):
+    """-> {name: array} as the reference's own GRAFDiscriminator computed them in fp32 on the CPU in training mode: the
+    names of run_steps, and `seed`."""
+    with np.load(fixture_path(B, imsize, ndf), allow_pickle=False) as f:
+        return {k: f[k] for k in f.files}

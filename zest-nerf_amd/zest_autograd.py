@@ -447,6 +447,35 @@ class PatchTermsFn(Function):
         return g_rgb, None, g_depth, None, None, None, None, None
 
 
+class GrafDiscFn(Function):
+    """GRAF patch discriminator (csrc/disc.hip).  x [B,imsize,imsize,3] contiguous fp32, then (imsize, ndf, training),
+    the spectral-norm buffers (us, vs: lists, no part of the graph; moved IN PLACE by a training-mode forward, also
+    under no_grad, as torch's hook moves them) and the weight_orig tensors -> logits [B].
+    Each forward keeps its own `saved` buffer: the raw layer outputs, the norm constants and the u, v and sigma that THIS
+    forward used.  A second forward moves the module's buffers before the first one's backward runs (the discriminator
+    step: fake, real, one backward); each backward reads its own forward's copies, as torch's hook ensures by cloning.
+    backward launches only what needs_input_grad asks for: no weight gradient with frozen weights (the generator step),
+    no first-layer data gradient with a detached input (the discriminator step)."""
+
+    @staticmethod
+    def forward(ctx, x, imsize, ndf, training, us, vs, *weights):
+        logits, saved = zest_hip.disc_fwd(x, weights, us, vs, imsize, ndf, training)
+        ctx.cfg = (imsize, ndf)
+        ctx.save_for_backward(x, saved, *weights)
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, saved, *weights = ctx.saved_tensors
+        imsize, ndf = ctx.cfg
+        need_w = ctx.needs_input_grad[6:]
+        g_x, g_w = zest_hip.disc_bwd(x, weights, saved, g.contiguous(), imsize, ndf, want_x=ctx.needs_input_grad[0],
+                                     want_w=any(need_w))
+        g_w = [gw if need else None for gw, need in zip(g_w, need_w)] if g_w is not None else [None] * len(weights)
+        return (g_x, None, None, None, None, None, *g_w)
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

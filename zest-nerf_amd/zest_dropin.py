@@ -7,7 +7,7 @@ The reference binds its hot path by module attribute: `from renderer import rend
 named `networks`, `utils`, `renderer` or `losses` - it shadows nothing.  `install()` imports the
 CALLER'S OWN modules of those names and rebinds, inside them, only the names of the rendering
 path to the HIP implementations (zest_renderer, zest_networks, zest_utils, zest_losses); every
-other name - discriminators, visualisation helpers, image-space losses, data loaders - stays the
+other name - discriminators (GRAF's can be opted in, below), visualisation helpers, image-space losses, data loaders - stays the
 caller's.  A script that runs afterwards (`from networks import ...`) picks the rebound names up.
 
     import zest_dropin; zest_dropin.install()           # then: import train
@@ -24,7 +24,7 @@ import runpy
 import sys
 import types
 
-__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "main"]
+__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "DISCRIMINATOR_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -45,6 +45,8 @@ _REIMPORTED = {
 SF_LOSS_NAMES = ("compute_sf_smooth_loss", "compute_sf_lke_loss")
 # opt-in (install(patch_losses=True) / ZEST_DROPIN_PATCH_LOSSES=1): the image-space regularisers of the static step
 PATCH_LOSS_NAMES = ("total_variation_loss", "get_disparity_smoothness")
+# opt-in (install(discriminator=True) / ZEST_DROPIN_DISCRIMINATOR=1): the GRAF patch discriminator (csrc/disc.hip)
+DISCRIMINATOR_NAMES = ("GRAFDiscriminator",)
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -68,12 +70,13 @@ def _bind(mod, name, value):
 
 
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False, patch_losses=False):
+            sf_losses=False, patch_losses=False, discriminator=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
     they stay the caller's).  patch_losses: also rebind `losses.total_variation_loss` and
-    `losses.get_disparity_smoothness` (off by default likewise).
+    `losses.get_disparity_smoothness` (off by default likewise).  discriminator: also rebind
+    `networks.GRAFDiscriminator` (off by default: it stays the caller's, as the other discriminators always do).
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +99,8 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
             names = names + SF_LOSS_NAMES
         if name == "losses" and patch_losses:
             names = names + PATCH_LOSS_NAMES
+        if name == "networks" and discriminator:
+            names = names + DISCRIMINATOR_NAMES
         target = targets[name]
         zest = importlib.import_module(zest_name)
         for n in names:
@@ -127,11 +132,13 @@ def main(argv=None):
               "runs SCRIPT (e.g. the reference's train.py / test.py) with the MI355X rendering path bound into its "
               "own networks / utils / renderer / losses modules; ZEST_DROPIN_SF_LOSSES=1 also binds the scene-flow "
               "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss), ZEST_DROPIN_PATCH_LOSSES=1 the patch "
-              "regularisers of the static step (total_variation_loss, get_disparity_smoothness)")
+              "regularisers of the static step (total_variation_loss, get_disparity_smoothness), ZEST_DROPIN_DISCRIMINATOR=1 "
+              "the GRAF patch discriminator (networks.GRAFDiscriminator)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
     install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
-            patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1")
+            patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1",
+            discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

@@ -87,6 +87,9 @@ _SIGS = {
     "zest_sf_ray_bwd": (_i, [_vp] * 17 + [_i, _i, _i, _i, _vp, _f, _f, _f, _f] + [_vp] * 10 + [_vp]),
     "zest_patch_terms_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "zest_patch_terms_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "zest_disc_layout": (_i, [_i, _i, _i, C.POINTER(C.c_longlong)]),
+    "zest_disc_fwd": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _vp, _vp, _vp]),
+    "zest_disc_bwd": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -532,6 +535,93 @@ def patch_terms_bwd(rgb, target, depth, terms=PT_ALL, coeff=(1.0, 1.0, 1.0), wan
     out = _grad_buffers("patch_terms_bwd", (rgb, depth), want, grads, first.device)
     _check(lib().zest_patch_terms_bwd(_ptr(rgb), _ptr(target), _ptr(depth), terms, P, H, W, *[float(v) for v in coeff],
                                       _ptr(out[0]), _ptr(out[1]), _stream(first)), "zest_patch_terms_bwd")
+    return out
+
+
+# ------------------------------------------------------------------------ GRAF discriminator (csrc/disc.hip)
+DISC_MAX_LAYERS = 6
+
+
+def disc_layout(B, imsize, ndf):
+    """Host arithmetic of csrc/disc.hip (no GPU call) -> {saved, work_fwd, work_bwd: floats; layers: [{cin, cout, side,
+    u, v, sigma, y, stats: offsets in `saved` (y: None for the last layer, stats: None without a norm)}]}.  Raises for an
+    imsize, ndf or batch the kernels do not take."""
+    out = (C.c_longlong * (8 + 8 * DISC_MAX_LAYERS))()
+    _check(lib().zest_disc_layout(int(B), int(imsize), int(ndf), out), "zest_disc_layout")
+    layers = []
+    for l in range(out[3]):
+        cin, cout, side, u, v, sigma, y, stats = out[8 + 8 * l:16 + 8 * l]
+        layers.append(dict(cin=cin, cout=cout, side=side, u=u, v=v, sigma=sigma, y=None if l == out[3] - 1 else y,
+                           stats=None if stats < 0 else stats))
+    return dict(saved=out[0], work_fwd=out[1], work_bwd=out[2], layers=layers)
+
+
+def _disc_tables(who, x, imsize, ndf, groups):
+    """x [B,imsize,imsize,3] and per-layer tensor lists (name, tensors, shape of layer l) -> (x, layout, pointer tables);
+    every tensor is checked against the layer table before its pointer crosses the boundary."""
+    x = _dev(x, "x", (None, imsize, imsize, 3))
+    lay = disc_layout(x.shape[0], imsize, ndf)
+    tables = []
+    for name, tensors, shape in groups:
+        if tensors is None:
+            tables.append(None)
+            continue
+        if len(tensors) != len(lay["layers"]):
+            raise RuntimeError("zest_hip: %s: %d %s tensors for %d layers" % (who, len(tensors), name, len(lay["layers"])))
+        for l, (t, L) in enumerate(zip(tensors, lay["layers"])):
+            if not t.is_cuda or t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() \
+                    or tuple(t.shape) != shape(L):
+                raise RuntimeError("zest_hip: %s: %s[%d] must be a contiguous fp32 tensor %s on %s, got %s %s on %s"
+                                   % (who, name, l, shape(L), x.device, t.dtype, tuple(t.shape), t.device))
+        tables.append((_vp * len(tensors))(*[_ptr(t) for t in tensors]))
+    return x, lay, tables
+
+
+_DISC_W = lambda L: (L["cout"], L["cin"], 4, 4)         # noqa: E731
+_DISC_U = lambda L: (L["cout"],)                          # noqa: E731
+_DISC_V = lambda L: (16 * L["cin"],)                      # noqa: E731
+
+
+def disc_fwd(x, weights, us, vs, imsize, ndf, training):
+    """GRAF discriminator forward.  x [B,imsize,imsize,3]; weights, us, vs: per layer weight_orig [cout,cin,4,4],
+    weight_u [cout], weight_v [16 cin], contiguous fp32 on x's device; training: one power iteration first, which moves
+    us and vs IN PLACE.  -> (logits [B], saved: what disc_bwd of this forward needs, with the u, v and sigma it used)."""
+    x, lay, (tw, tu, tv) = _disc_tables("disc_fwd", x, imsize, ndf, (("weights", weights, _DISC_W), ("us", us, _DISC_U),
+                                                                     ("vs", vs, _DISC_V)))
+    saved = torch.empty(lay["saved"], device=x.device, dtype=torch.float32)
+    work = torch.empty(lay["work_fwd"], device=x.device, dtype=torch.float32)
+    logits = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+    _check(lib().zest_disc_fwd(_ptr(x), x.shape[0], imsize, ndf, tw, tu, tv, int(bool(training)), _ptr(saved), _ptr(work),
+                               _ptr(logits), _stream(x)), "zest_disc_fwd")
+    return logits, saved
+
+
+def disc_bwd(x, weights, saved, g_logits, imsize, ndf, want_x=True, want_w=True):
+    """Backward of the forward that left `saved` -> (g_x [B,imsize,imsize,3] or None, [d / d weight_orig per layer] or
+    None).  want_x false skips the first layer's data gradient, want_w false every weight-gradient launch."""
+    if not (want_x or want_w):
+        return None, None
+    x, lay, (tw,) = _disc_tables("disc_bwd", x, imsize, ndf, (("weights", weights, _DISC_W),))
+    saved = _dev(saved, "saved", (lay["saved"],))
+    g_logits = _dev(g_logits, "g_logits", (x.shape[0],))
+    work = torch.empty(lay["work_bwd"], device=x.device, dtype=torch.float32)
+    g_x = torch.empty_like(x) if want_x else None
+    g_w = [torch.empty_like(w) for w in weights] if want_w else None
+    tg = (_vp * len(g_w))(*[_ptr(t) for t in g_w]) if want_w else None
+    _check(lib().zest_disc_bwd(_ptr(x), x.shape[0], imsize, ndf, tw, _ptr(saved), _ptr(g_logits), _ptr(work), _ptr(g_x), tg,
+                               _stream(x)), "zest_disc_bwd")
+    return g_x, g_w
+
+
+def disc_saved_views(saved, B, imsize, ndf):
+    """The tensors inside `saved` of disc_fwd, per layer: {u, v, sigma, y (raw output [B,side,side,cout]; None for the
+    last layer), stats ([B,cout,2] mean and 1/deviation; None without a norm)} - views, for the tests."""
+    out = []
+    for L in disc_layout(B, imsize, ndf)["layers"]:
+        n_y = B * L["side"] * L["side"] * L["cout"]
+        out.append(dict(u=saved[L["u"]:L["u"] + L["cout"]], v=saved[L["v"]:L["v"] + 16 * L["cin"]], sigma=saved[L["sigma"]],
+                        y=None if L["y"] is None else saved[L["y"]:L["y"] + n_y].view(B, L["side"], L["side"], L["cout"]),
+                        stats=None if L["stats"] is None else saved[L["stats"]:L["stats"] + 2 * B * L["cout"]].view(B, L["cout"], 2)))
     return out
 
 

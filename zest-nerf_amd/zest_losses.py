@@ -25,8 +25,10 @@ them there (`ray_terms="hip"`, the default) or through the torch composition it 
 evaluates what the static ("svs") training step evaluates on its rendered patches - reconstruction error, total
 variation of the depth patch, edge-aware depth smoothness and the PSNR it logs (train.py:599-617, 754) - in two launches
 of csrc/patch_losses.hip, values and gradients; `train_step_loss` is the part of MVSNeRFSystem.training_step
-(train.py:587-760) this package evaluates, on top of `patch_terms` and `distortion_loss`.  The adversarial and
-perceptual terms of that step need the caller's discriminator and a pretrained network: they stay the caller's, as do
+(train.py:587-760) this package evaluates, on top of `patch_terms` and `distortion_loss`.  Given a
+`zest_networks.GRAFDiscriminator` it adds the adversarial term of the generator step (train.py:646-654), and
+`discriminator_step_loss` is the discriminator's own step (train.py:698-719), both on the kernels of csrc/disc.hip.
+The perceptual term needs a pretrained network: it stays the caller's, as do the other discriminators and
 `mse_masked`, `mae_masked` and `compute_depth_loss` as names (the scene-flow step evaluates them inside its kernels).
 """
 import torch
@@ -37,7 +39,7 @@ import zest_utils
 
 __all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers",
            "scene_flow_sample_terms", "scene_flow_ray_terms", "train_sf_step_loss", "total_variation_loss",
-           "get_disparity_smoothness", "patch_terms", "train_step_loss"]
+           "get_disparity_smoothness", "patch_terms", "train_step_loss", "discriminator_step_loss"]
 
 
 def distortion_loss(ray_weights, t_vals):
@@ -380,9 +382,45 @@ def _patch_terms(who, rgb_pred, rgb_gt, depth_pred, patch_size, terms, w_rec, w_
     return total, mse, tv, smooth, -10.0 * torch.log10(mse) if terms & zest_hip.PT_MSE else None
 
 
-def train_step_loss(results, hparams, adversarial=False):
+def _lsgan(who, hparams):
+    """hparams.gan_loss, where given, must be lsgan: the reference's `naive` loss is a BCE on the logits of a net
+    without a sigmoid, outside its domain.  Refuse it."""
+    kind = "lsgan" if hparams is None else \
+        hparams.get("gan_loss", "lsgan") if isinstance(hparams, dict) else getattr(hparams, "gan_loss", "lsgan")
+    if kind not in (None, "lsgan"):
+        raise NotImplementedError("%s: gan_loss %r: only lsgan (mean squared error) is evaluated; the reference's 'naive' "
+                                  "BCE on the logits of this sigmoid-less discriminator is outside its domain" % (who, kind))
+
+
+def _discriminator(who, discriminator):
+    import zest_networks
+    if not isinstance(discriminator, zest_networks.GRAFDiscriminator):
+        raise RuntimeError("%s: discriminator must be a zest_networks.GRAFDiscriminator, got %s"
+                           % (who, type(discriminator).__name__))
+    return discriminator
+
+
+def discriminator_step_loss(discriminator, rgb_pred, rgb_gt, hparams=None):
+    """The discriminator step of the static training step (optimizer_idx 1, train.py:698-719), lsgan: both inputs
+    [..., R, C >= 3] are detached, the fake patch goes through first, then the real one;
+    -> ((D_fake_loss + D_real_loss) / 2 with the graph to the discriminator's weights,
+        {D_fake_loss = mean D(rgb_pred)^2, D_real_loss = mean (D(rgb_gt) - 1)^2}, detached)."""
+    who = "discriminator_step_loss"
+    D = _discriminator(who, discriminator)
+    _lsgan(who, hparams)
+    _check_shapes(who, [("rgb_pred", rgb_pred, 0), ("rgb_gt", rgb_gt, 0)], 2, "[..., N_rays, C")
+    d_fake = (D(rgb_pred.detach()) ** 2).mean()
+    d_real = ((D(rgb_gt.detach()) - 1.0) ** 2).mean()
+    return (d_fake + d_real) / 2, {"D_fake_loss": d_fake.detach(), "D_real_loss": d_real.detach()}
+
+
+def train_step_loss(results, hparams, adversarial=False, discriminator=None):
     """The part of one static ("svs") training step that this package evaluates: MVSNeRFSystem.training_step
-    (train.py:587-760) without its class, its discriminators and its perceptual network.
+    (train.py:587-760) without its class, its perceptual network and the discriminators other than GRAF's.
+    discriminator: None, or (adversarial only) a zest_networks.GRAFDiscriminator: the generator's adversarial term
+    lambda_adv mean (D(rgb_map) - 1)^2 (lsgan; train.py:646-654) is added to the loss and logged as G_fake_loss.  Its
+    gradient goes to rgb_map, and to the discriminator's weights unless they are frozen (Lightning's toggle_optimizer
+    freezes them in this step: then no weight-gradient kernel runs).
     results: what the model returned; read are rgb_map [..., R, 3], target_s [..., R, 3], depth_map [..., R],
     weights [1, R, S] and t_vals (the last two only with_distortion_loss).  hparams (attributes or keys): patch_size,
     with_depth_loss_reg / lambda_depth_reg (total variation of the depth patches), with_depth_smoothness /
@@ -392,16 +430,23 @@ def train_step_loss(results, hparams, adversarial=False):
           the reference multiplies every regulariser by its coefficient where it computes and logs it and AGAIN in the
           total.  That is what the reference trains with, so it is what this function returns.
       adversarial=True: the terms of the generator step (optimizer_idx 0, train.py:683-694) that need no network,
-          l_rec mse + l_reg tv + l_smooth smooth + l_dist distortion; the caller adds G_fake_loss, the feature-matching
-          and the perceptual term.
+          l_rec mse + l_reg tv + l_smooth smooth + l_dist distortion, plus G_fake_loss where a discriminator is given
+          (else the caller's to add); the caller adds the feature-matching and the perceptual term.
     hparams.train_sceneflow must be false (that step is train_sf_step_loss).  with_perceptual_loss, with_depth_loss_rec
     and the depth discriminator are not evaluated here and are ignored: their terms are the caller's to add.
     -> (loss with the graph, {name: logged value}) with the reference's names, weighted as it logs them: tv_depth_loss,
-    depth_smooth_loss, distortion_loss (each where its flag is set), G_rec_loss (adversarial only) and train_PSNR =
+    depth_smooth_loss, distortion_loss (each where its flag is set), G_rec_loss (adversarial only), G_fake_loss (with a
+    discriminator) and train_PSNR =
     10 log10(1 / mse)."""
     hp = _hparams(hparams)
     if hp("train_sceneflow"):
         raise RuntimeError("train_step_loss: hparams.train_sceneflow is set: that step's loss is train_sf_step_loss")
+    if discriminator is not None:
+        if not adversarial:
+            raise RuntimeError("train_step_loss: a discriminator was given with adversarial=False: plain training "
+                               "(gan_type None) has no adversarial term")
+        _discriminator("train_step_loss", discriminator)
+        _lsgan("train_step_loss", hparams)
     l_reg = float(hp("lambda_depth_reg")) if hp("with_depth_loss_reg") else 0.0
     l_smooth = float(hp("lambda_depth_smooth")) if hp("with_depth_smoothness") else 0.0
     l_dist = float(hp("lambda_distortion")) if hp("with_distortion_loss") else 0.0
@@ -422,5 +467,9 @@ def train_step_loss(results, hparams, adversarial=False):
         total = total + again(l_dist) * dist
     if adversarial:
         logs["G_rec_loss"] = l_rec * mse
+    if discriminator is not None:
+        g_fake = float(hp("lambda_adv")) * ((discriminator(results["rgb_map"]) - 1.0) ** 2).mean()
+        logs["G_fake_loss"] = g_fake.detach()
+        total = total + g_fake
     logs["train_PSNR"] = psnr
     return total, logs

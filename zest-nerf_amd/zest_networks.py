@@ -25,7 +25,7 @@ import zest_hip
 
 __all__ = ["Embedding", "Renderer", "Renderer_linear", "MVSNeRF", "resolve_precision", "inference_precision",
            "ActivatedBatchNorm", "ConvBnReLU", "ConvBnReLU3D", "FeatureNet", "CostRegNet", "MVSNet",
-           "MVSNeRF_G", "DyMVSNeRF_G"]
+           "MVSNeRF_G", "DyMVSNeRF_G", "GRAFDiscriminator"]
 
 
 _PREC_BY_NAME = {"bf16": zest_hip.PREC_BF16, "16": zest_hip.PREC_BF16,
@@ -947,3 +947,69 @@ class DyMVSNeRF_G(_Generator):
                 for k, part in zip(self.VAL_KEYS, torch.split(full, widths, 1)):
                     outs[k] = [part if part.shape[1] > 1 else part[:, 0]]
         return (sc['imgs'],) + tuple(outs[k] for k in self.VAL_KEYS)
+
+
+# ------------------------------------------------------------------------------------------ GRAF discriminator
+class _SpectralConv(nn.Module):
+    """The state of one `spectral_norm(Conv2d(cin, cout, 4, stride, pad, bias=False))` of the reference: weight_orig,
+    weight_u, weight_v under torch's names, initialised as torch initialises them (Conv2d.reset_parameters, then
+    SpectralNorm.apply: u and v normal deviates scaled to unit length, drawn in that order)."""
+
+    def __init__(self, cin, cout):
+        super().__init__()
+        w = torch.empty(cout, cin, 4, 4)
+        nn.init.kaiming_uniform_(w, a=5 ** 0.5)
+        self.weight_orig = nn.Parameter(w)
+        self.register_buffer("weight_u", nn.functional.normalize(w.new_empty(cout).normal_(0, 1), dim=0, eps=1e-12))
+        self.register_buffer("weight_v", nn.functional.normalize(w.new_empty(16 * cin).normal_(0, 1), dim=0, eps=1e-12))
+
+
+class GRAFDiscriminator(nn.Module):
+    """The GRAF patch discriminator (reference networks.py:845-929) on the kernels of csrc/disc.hip: same signature,
+    same state-dict keys (`main.<i>.weight_orig / weight_u / weight_v`, <i> the reference's Sequential indices), so
+    a reference checkpoint loads with strict=True.  forward(input [..., N, C >= nc]) -> logits [B,1,1,1], one per
+    imsize x imsize patch of the rays in their order.  train(): each forward runs one power iteration of the spectral
+    norm first and moves weight_u / weight_v in place, also under no_grad; eval(): the stored u and v give sigma.
+    There is no torch path: CPU tensors raise.  Not built: hflip (host RNG; train.py never sets it), nc != 3."""
+
+    # Sequential indices of the spectrally normalised convolutions, by imsize
+    INDICES = {32: (0, 3, 6, 9), 64: (0, 2, 5, 8, 11), 128: (0, 2, 5, 8, 11, 14)}
+
+    def __init__(self, nc=3, ndf=64, imsize=64, hflip=False):
+        super().__init__()
+        if hflip:
+            raise NotImplementedError("GRAFDiscriminator: hflip=True draws its flips from the host RNG and is not built "
+                                      "(the reference's train.py never sets it)")
+        if nc != 3:
+            raise NotImplementedError("GRAFDiscriminator: nc = %r; the kernels are built for 3-channel patches" % (nc,))
+        if imsize not in self.INDICES:
+            raise RuntimeError("GRAFDiscriminator: imsize %r is not 32, 64 or 128" % (imsize,))
+        step = 32 if imsize == 128 else 16
+        if int(ndf) != ndf or ndf < step or ndf % step or ndf > 256:
+            raise NotImplementedError("GRAFDiscriminator: ndf = %r; the kernels take multiples of %d up to 256 at imsize %d"
+                                      % (ndf, step, imsize))
+        self.nc, self.ndf, self.imsize, self.hflip = nc, int(ndf), imsize, False
+        chans = {32: (3, 2 * ndf), 64: (3, ndf, 2 * ndf), 128: (3, ndf // 2, ndf, 2 * ndf)}[imsize] + (4 * ndf, 8 * ndf, 1)
+        self.main = nn.ModuleDict({str(i): _SpectralConv(cin, cout)
+                                   for i, cin, cout in zip(self.INDICES[imsize], chans[:-1], chans[1:])})
+
+    def layers(self):
+        return [self.main[str(i)] for i in self.INDICES[self.imsize]]
+
+    def forward(self, input):
+        import zest_autograd
+        import zest_losses
+        who, n = "GRAFDiscriminator", self.imsize * self.imsize
+        zest_losses._check_shapes(who, [("input", input, 0)], 2, "[..., N_rays, C >= %d" % self.nc)
+        if input.shape[-1] < self.nc:
+            raise RuntimeError("%s: input %s has fewer than %d channels" % (who, tuple(input.shape), self.nc))
+        rays = input.numel() // input.shape[-1]
+        if rays % n:
+            raise RuntimeError("%s: %d rays are not a multiple of imsize^2 = %d" % (who, rays, n))
+        layers = self.layers()
+        named = [("input", input, 0)] + [("main.%d.weight_orig" % i, m.weight_orig, 0) for i, m in zip(self.INDICES[self.imsize], layers)]
+        zest_losses._check_devices(who, named)
+        x = input[..., :self.nc].float().reshape(-1, self.imsize, self.imsize, self.nc).contiguous()
+        logits = zest_autograd.GrafDiscFn.apply(x, self.imsize, self.ndf, self.training, [m.weight_u for m in layers],
+                                                [m.weight_v for m in layers], *[m.weight_orig for m in layers])
+        return logits.reshape(-1, 1, 1, 1)

@@ -430,6 +430,43 @@ int zest_disc_fwd(const float *x, int B, int imsize, int ndf, const float *const
 int zest_disc_bwd(const float *x, int B, int imsize, int ndf, const float *const *w, const float *saved,
                   const float *g_logits, float *work, float *g_x, float *const *g_w, void *stream);
 
+/* LPIPS v0.1, AlexNet backbone (net='alex', lpips=True, spatial=False, eval mode): the perceptual term of
+ * the static training step (reference train.py:86, 626-632, 694) and its val_lpips / test_lpips metric.
+ *   x <- 2 x - 1 if normalize; (x - shift) / scale per channel (conv1's zero padding is 0 in THAT domain);
+ *   five ReLU taps: conv 3 -> 64 11x11 stride 4 pad 2 | maxpool 3x3 stride 2, conv 64 -> 192 5x5 pad 2 |
+ *   maxpool 3x3 stride 2, conv 192 -> 384 3x3 pad 1 | conv 384 -> 256 3x3 pad 1 | conv 256 -> 256 3x3 pad 1,
+ *   all with a bias, floor output sizes; per tap f = y / (sqrt(sum_c y^2) + 1e-10) and
+ *   d_k = mean over pixels of sum_c lin_k[c] (f0 - f1)^2.
+ * in0, in1: [N,3,H,W] fp32 addressed through strides in elements (stride[0..3] of n, c, h, w): NCHW,
+ * channels-last and ray-ordered patches are all read in place.  H, W >= 31.  Both go through the forward as
+ * one batch of 2 N images.  All arithmetic is fp32 (fp32 MFMA, exact products); no float atomics: two calls
+ * from the same state are bit-identical, value and gradient.
+ * zest_lpips_layout: host arithmetic only.  out[0..2] = floats of `saved`, of `work` (enough for either
+ *   launch sequence) and of `packed`; out[3] = 5; out[4], out[5] = the offsets in `packed` of shift and
+ *   scale (4 floats each); out[8 + 8 l ..] per tap: channels, map height, map width, the offset in `saved`
+ *   of the tap [2N,h,w,channels] (post ReLU, channels-last), the packed row length K, and the offsets in
+ *   `packed` of the weights [cout][K] (k = (ky KW + kx) cin + ci; conv1's 363 padded with zeros to 368),
+ *   the bias [cout] and lin [cout].  out holds 8 + 8 ZEST_LPIPS_LAYERS entries.
+ * zest_lpips_pack: w, bias, lin: one device pointer per layer (weight [cout][cin][KH][KW], bias [cout],
+ *   lin [1][cout][1][1]); shift, scale [3] -> packed.  Once per weight state.
+ * zest_lpips_fwd: result [N][1 + ZEST_LPIPS_LAYERS]: sum_k d_k, then d_1 .. d_5.  `saved` keeps what
+ *   zest_lpips_bwd of this forward needs; NULL: no backward will follow, nothing is kept.
+ * zest_lpips_bwd: g [N][1 + ZEST_LPIPS_LAYERS], the upstream gradient of `result` -> g_in0, written through
+ *   gstride as in0 is read, every element once.  Only in0 takes a gradient: in1 is the target, the weights
+ *   are frozen.  The ReLU gate is a select: a pixel whose channels are all 0 gets exactly 0.  Max pooling
+ *   sends the gradient to the first maximum of a window in row-major order.
+ * Errors: H or W < 31; N < 1; NULL pointers (but `saved` of the forward); in0, in1, g, g_in0, result not
+ * 4-byte aligned; packed, saved, work not 16-byte aligned. */
+#define ZEST_LPIPS_LAYERS 5
+int zest_lpips_layout(int N, int H, int W, long long *out);
+int zest_lpips_pack(const float *const *w, const float *const *bias, const float *const *lin, const float *shift,
+                    const float *scale, float *packed, void *stream);
+int zest_lpips_fwd(const float *in0, const long long *stride0, const float *in1, const long long *stride1, int N,
+                   int H, int W, int normalize, const float *packed, float *saved, float *work, float *result,
+                   void *stream);
+int zest_lpips_bwd(const float *packed, const float *saved, const float *g, int N, int H, int W, int normalize,
+                   float *work, float *g_in0, const long long *gstride, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

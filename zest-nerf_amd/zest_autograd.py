@@ -476,6 +476,32 @@ class GrafDiscFn(Function):
         return (g_x, None, None, None, None, None, *g_w)
 
 
+class LpipsFn(Function):
+    """LPIPS with the AlexNet backbone (csrc/lpips.hip).  in0, in1 [N,3,H,W] fp32 of any strides (read in place), the
+    packed weight state, normalize and the caller's torch.is_grad_enabled() (as SceneFlowRayFn) -> result [N,6]: the sum of
+    the five layers' terms, then each term.  Only in0 takes a gradient: in1 is the target and the weights are frozen.
+    Each forward keeps its own `saved` buffer (the five taps of both images), and only when in0 requires a gradient and
+    the graph is recorded; otherwise nothing is kept."""
+
+    @staticmethod
+    def forward(ctx, in0, in1, packed, normalize, recording):
+        save = bool(recording) and ctx.needs_input_grad[0]
+        result, saved = zest_hip.lpips_fwd(in0, in1, packed, normalize, save=save)
+        ctx.normalize = bool(normalize)
+        if save:
+            ctx.like = (tuple(in0.shape), tuple(in0.stride()))   # the backward reads no pixel: conv1 is linear
+            ctx.save_for_backward(packed, saved)
+        return result
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        packed, saved = ctx.saved_tensors
+        return zest_hip.lpips_bwd(packed, saved, g.contiguous(), *ctx.like, ctx.normalize), None, None, None, None
+
+
 class ProjectRaysFn(Function):
     """projection_from_ndc: expected point -> Euclidean -> camera -> pixels, fused per ray."""
 

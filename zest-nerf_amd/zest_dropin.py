@@ -7,7 +7,7 @@ The reference binds its hot path by module attribute: `from renderer import rend
 named `networks`, `utils`, `renderer` or `losses` - it shadows nothing.  `install()` imports the
 CALLER'S OWN modules of those names and rebinds, inside them, only the names of the rendering
 path to the HIP implementations (zest_renderer, zest_networks, zest_utils, zest_losses); every
-other name - discriminators (GRAF's can be opted in, below), visualisation helpers, image-space losses, data loaders - stays the
+other name - discriminators (GRAF's can be opted in, below, and so can the `lpips` package's network), visualisation helpers, image-space losses, data loaders - stays the
 caller's.  A script that runs afterwards (`from networks import ...`) picks the rebound names up.
 
     import zest_dropin; zest_dropin.install()           # then: import train
@@ -24,7 +24,8 @@ import runpy
 import sys
 import types
 
-__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "DISCRIMINATOR_NAMES", "main"]
+__all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "DISCRIMINATOR_NAMES",
+           "PERCEPTUAL_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -47,6 +48,9 @@ SF_LOSS_NAMES = ("compute_sf_smooth_loss", "compute_sf_lke_loss")
 PATCH_LOSS_NAMES = ("total_variation_loss", "get_disparity_smoothness")
 # opt-in (install(discriminator=True) / ZEST_DROPIN_DISCRIMINATOR=1): the GRAF patch discriminator (csrc/disc.hip)
 DISCRIMINATOR_NAMES = ("GRAFDiscriminator",)
+# opt-in (install(perceptual=True) / ZEST_DROPIN_PERCEPTUAL=1): `lpips.LPIPS` of the caller's own `lpips` package
+# becomes a factory that returns a zest_networks.LPIPS (csrc/lpips.hip) holding the package's pretrained weights
+PERCEPTUAL_NAMES = ("LPIPS",)
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -69,14 +73,32 @@ def _bind(mod, name, value):
     setattr(mod, name, value)
 
 
+def _lpips_factory(package_cls):
+    """-> a callable with lpips.LPIPS's signature: the package builds its own pretrained module, whose state dict is
+    copied into a zest_networks.LPIPS.  Refusals (another net, spatial=True) come before the package does any work."""
+    import zest_networks
+
+    def LPIPS(*args, **kwargs):
+        ours = zest_networks.LPIPS(*args, **kwargs)
+        theirs = package_cls(*args, **kwargs)
+        ours.load_state_dict(theirs.state_dict(), strict=True)
+        return ours.eval()
+    LPIPS.__doc__ = "zest_dropin: lpips.LPIPS -> zest_networks.LPIPS with the package's weights"
+    LPIPS.__wrapped__ = package_cls
+    return LPIPS
+
+
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False, patch_losses=False, discriminator=False):
+            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
     they stay the caller's).  patch_losses: also rebind `losses.total_variation_loss` and
     `losses.get_disparity_smoothness` (off by default likewise).  discriminator: also rebind
     `networks.GRAFDiscriminator` (off by default: it stays the caller's, as the other discriminators always do).
+    perceptual: also rebind `LPIPS` in the caller's `lpips` package (imported here; ImportError if it is missing) to a
+    factory that lets the package build its pretrained module and returns a zest_networks.LPIPS with that state (off
+    by default: `lpips.LPIPS` stays the package's).
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -112,6 +134,11 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
                     _bind(target, n, getattr(src, n))
         target.__zest_dropin__ = sorted(names)
         done[name] = sorted(names)
+    if perceptual:
+        package = importlib.import_module("lpips")
+        for n in PERCEPTUAL_NAMES:
+            _bind(package, n, _lpips_factory(getattr(package, n)))
+        done["lpips"] = sorted(PERCEPTUAL_NAMES)
     return done
 
 
@@ -133,12 +160,14 @@ def main(argv=None):
               "own networks / utils / renderer / losses modules; ZEST_DROPIN_SF_LOSSES=1 also binds the scene-flow "
               "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss), ZEST_DROPIN_PATCH_LOSSES=1 the patch "
               "regularisers of the static step (total_variation_loss, get_disparity_smoothness), ZEST_DROPIN_DISCRIMINATOR=1 "
-              "the GRAF patch discriminator (networks.GRAFDiscriminator)")
+              "the GRAF patch discriminator (networks.GRAFDiscriminator), ZEST_DROPIN_PERCEPTUAL=1 the LPIPS network "
+              "(lpips.LPIPS, AlexNet backbone)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
     install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
             patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1",
-            discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1")
+            discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1",
+            perceptual=os.environ.get("ZEST_DROPIN_PERCEPTUAL", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

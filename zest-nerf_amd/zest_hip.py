@@ -90,6 +90,10 @@ _SIGS = {
     "zest_disc_layout": (_i, [_i, _i, _i, C.POINTER(C.c_longlong)]),
     "zest_disc_fwd": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _vp, _vp, _vp]),
     "zest_disc_bwd": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "zest_lpips_layout": (_i, [_i, _i, _i, C.POINTER(C.c_longlong)]),
+    "zest_lpips_pack": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp]),
+    "zest_lpips_fwd": (_i, [_vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "zest_lpips_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -622,6 +626,125 @@ def disc_saved_views(saved, B, imsize, ndf):
         out.append(dict(u=saved[L["u"]:L["u"] + L["cout"]], v=saved[L["v"]:L["v"] + 16 * L["cin"]], sigma=saved[L["sigma"]],
                         y=None if L["y"] is None else saved[L["y"]:L["y"] + n_y].view(B, L["side"], L["side"], L["cout"]),
                         stats=None if L["stats"] is None else saved[L["stats"]:L["stats"] + 2 * B * L["cout"]].view(B, L["cout"], 2)))
+    return out
+
+
+# ------------------------------------------------------------------------ LPIPS, AlexNet backbone (csrc/lpips.hip)
+LPIPS_LAYERS = 5
+LPIPS_MIN_SIDE = 31
+# (cin, cout, kernel side) of the five convolutions
+LPIPS_CONVS = ((3, 64, 11), (64, 192, 5), (192, 384, 3), (384, 256, 3), (256, 256, 3))
+
+
+def lpips_layout(N, H, W):
+    """Host arithmetic of csrc/lpips.hip (no GPU call) -> {saved, work, packed: floats; shift, scale: offsets in
+    `packed`; layers: [{channels, h, w, act: offset of the tap [2N,h,w,channels] in `saved`, K: the packed row length,
+    weight, bias, lin: offsets in `packed`}]}.  Raises for H or W < 31 and for N < 1."""
+    out = (C.c_longlong * (8 + 8 * LPIPS_LAYERS))()
+    _check(lib().zest_lpips_layout(int(N), int(H), int(W), out), "zest_lpips_layout")
+    layers = []
+    for l in range(out[3]):
+        ch, h, w, act, K, weight, bias, lin = out[8 + 8 * l:16 + 8 * l]
+        layers.append(dict(channels=ch, h=h, w=w, act=act, K=K, weight=weight, bias=bias, lin=lin))
+    return dict(saved=out[0], work=out[1], packed=out[2], shift=out[4], scale=out[5], layers=layers)
+
+
+def _lpips_table(who, name, tensors, shapes, device):
+    if len(tensors) != LPIPS_LAYERS:
+        raise RuntimeError("zest_hip: %s: %d %s tensors for %d layers" % (who, len(tensors), name, LPIPS_LAYERS))
+    for l, (t, shape) in enumerate(zip(tensors, shapes)):
+        if not t.is_cuda or t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError("zest_hip: %s: %s[%d] must be a contiguous fp32 tensor %s on %s, got %s %s on %s"
+                               % (who, name, l, shape, device, t.dtype, tuple(t.shape), t.device))
+    return (_vp * LPIPS_LAYERS)(*[_ptr(t) for t in tensors])
+
+
+def lpips_pack(weights, biases, lins, shift, scale):
+    """The five convolution weights [cout,cin,k,k], biases [cout], lin weights [1,cout,1,1], shift and scale [1,3,1,1],
+    contiguous fp32 on one device -> the packed weight state lpips_fwd / lpips_bwd read (one launch)."""
+    who = "lpips_pack"
+    if not torch.is_tensor(shift) or not shift.is_cuda:
+        raise RuntimeError("zest_hip: %s: shift is on %s; this path runs only on a HIP device"
+                           % (who, shift.device if torch.is_tensor(shift) else type(shift).__name__))
+    dev = shift.device
+    tw = _lpips_table(who, "weights", weights, [(co, ci, k, k) for ci, co, k in LPIPS_CONVS], dev)
+    tb = _lpips_table(who, "biases", biases, [(co,) for _, co, _ in LPIPS_CONVS], dev)
+    tl = _lpips_table(who, "lins", lins, [(1, co, 1, 1) for _, co, _ in LPIPS_CONVS], dev)
+    shift, scale = _dev(shift, "shift", (1, 3, 1, 1)), _dev(scale, "scale", (1, 3, 1, 1))
+    if scale.device != dev:
+        raise RuntimeError("zest_hip: %s: scale is on %s, shift on %s" % (who, scale.device, dev))
+    packed = torch.empty(lpips_layout(1, 64, 64)["packed"], device=dev, dtype=torch.float32)
+    _check(lib().zest_lpips_pack(tw, tb, tl, _ptr(shift), _ptr(scale), _ptr(packed), _stream(shift)), "zest_lpips_pack")
+    return packed
+
+
+def _lpips_image(who, name, t, like=None):
+    """An fp32 device tensor [N,3,H,W] of ANY strides (it is read in place) -> (tensor, its strides as a C array)."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
+        raise RuntimeError("zest_hip: %s: %s must be a tensor [N, 3, H, W], got %s"
+                           % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if not t.is_cuda:
+        raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise RuntimeError("zest_hip: %s: %s %s on %s does not match in0 %s on %s"
+                           % (who, name, tuple(t.shape), t.device, tuple(like.shape), like.device))
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t, (C.c_longlong * 4)(*t.stride())
+
+
+def lpips_fwd(in0, in1, packed, normalize=False, save=True):
+    """LPIPS forward.  in0, in1 [N,3,H,W] fp32 of any strides; packed = lpips_pack(...) -> (result [N,6]: the sum of the
+    five layers, then each layer's term; saved: what lpips_bwd of this forward needs, None unless `save`)."""
+    in0, s0 = _lpips_image("lpips_fwd", "in0", in0)
+    in1, s1 = _lpips_image("lpips_fwd", "in1", in1, in0)
+    N, _, H, W = in0.shape
+    lay = lpips_layout(N, H, W)
+    packed = _dev(packed, "packed", (lay["packed"],))
+    saved = torch.empty(lay["saved"], device=in0.device, dtype=torch.float32) if save else None
+    work = torch.empty(lay["work"], device=in0.device, dtype=torch.float32)
+    result = torch.empty(N, LPIPS_LAYERS + 1, device=in0.device, dtype=torch.float32)
+    _check(lib().zest_lpips_fwd(_ptr(in0), s0, _ptr(in1), s1, N, H, W, int(bool(normalize)), _ptr(packed), _ptr(saved),
+                                _ptr(work), _ptr(result), _stream(in0)), "zest_lpips_fwd")
+    return result, saved
+
+
+def _dense(shape, stride):
+    """Do these strides address every element of a block of prod(shape) elements exactly once?"""
+    expect = 1
+    for size, st in sorted(((s, t) for s, t in zip(shape, stride) if s > 1), key=lambda p: p[1]):
+        if st != expect:
+            return False
+        expect *= size
+    return True
+
+
+def lpips_bwd(packed, saved, g, shape, stride, normalize=False):
+    """Backward of the forward that left `saved`: g [N,6], the upstream gradient of its result; shape, stride: of that
+    forward's in0 -> d / d in0, in in0's own layout where that is dense (else contiguous)."""
+    N, ch, H, W = (int(s) for s in shape)
+    if ch != 3:
+        raise RuntimeError("zest_hip: lpips_bwd: shape %s is not [N, 3, H, W]" % (tuple(shape),))
+    lay = lpips_layout(N, H, W)
+    packed = _dev(packed, "packed", (lay["packed"],))
+    saved, g = _dev(saved, "saved", (lay["saved"],)), _dev(g, "g", (N, LPIPS_LAYERS + 1))
+    work = torch.empty(lay["work"], device=packed.device, dtype=torch.float32)
+    if _dense(shape, stride):
+        g_in0 = torch.empty_strided(tuple(shape), tuple(stride), device=packed.device, dtype=torch.float32)
+    else:
+        g_in0 = torch.empty(tuple(shape), device=packed.device, dtype=torch.float32)
+    _check(lib().zest_lpips_bwd(_ptr(packed), _ptr(saved), _ptr(g), N, H, W, int(bool(normalize)), _ptr(work), _ptr(g_in0),
+                                (C.c_longlong * 4)(*g_in0.stride()), _stream(packed)), "zest_lpips_bwd")
+    return g_in0
+
+
+def lpips_saved_views(saved, N, H, W):
+    """The taps inside `saved` of lpips_fwd: [tensor [2N,h,w,channels] per layer] (post ReLU; in0's images first) -
+    views, for the tests."""
+    out = []
+    for L in lpips_layout(N, H, W)["layers"]:
+        n = 2 * N * L["h"] * L["w"] * L["channels"]
+        out.append(saved[L["act"]:L["act"] + n].view(2 * N, L["h"], L["w"], L["channels"]))
     return out
 
 

@@ -28,8 +28,10 @@ of csrc/patch_losses.hip, values and gradients; `train_step_loss` is the part of
 (train.py:587-760) this package evaluates, on top of `patch_terms` and `distortion_loss`.  Given a
 `zest_networks.GRAFDiscriminator` it adds the adversarial term of the generator step (train.py:646-654), and
 `discriminator_step_loss` is the discriminator's own step (train.py:698-719), both on the kernels of csrc/disc.hip.
-The perceptual term needs a pretrained network: it stays the caller's, as do the other discriminators and
-`mse_masked`, `mae_masked` and `compute_depth_loss` as names (the scene-flow step evaluates them inside its kernels).
+Given a `zest_networks.LPIPS` (which holds the pretrained weights the caller loaded) it evaluates the perceptual term
+as well (train.py:626-632; `perceptual_loss` is that term on its own), on the kernels of csrc/lpips.hip.  The other
+discriminators stay the caller's, as do `mse_masked`, `mae_masked` and `compute_depth_loss` as names (the scene-flow
+step evaluates them inside its kernels).
 """
 import torch
 
@@ -39,7 +41,7 @@ import zest_utils
 
 __all__ = ["distortion_loss", "compute_sf_smooth_loss", "compute_sf_lke_loss", "scene_flow_regularisers",
            "scene_flow_sample_terms", "scene_flow_ray_terms", "train_sf_step_loss", "total_variation_loss",
-           "get_disparity_smoothness", "patch_terms", "train_step_loss", "discriminator_step_loss"]
+           "get_disparity_smoothness", "patch_terms", "train_step_loss", "discriminator_step_loss", "perceptual_loss"]
 
 
 def distortion_loss(ray_weights, t_vals):
@@ -414,13 +416,45 @@ def discriminator_step_loss(discriminator, rgb_pred, rgb_gt, hparams=None):
     return (d_fake + d_real) / 2, {"D_fake_loss": d_fake.detach(), "D_real_loss": d_real.detach()}
 
 
-def train_step_loss(results, hparams, adversarial=False, discriminator=None):
+def _perceptual(who, net):
+    import zest_networks
+    if not isinstance(net, zest_networks.LPIPS):
+        raise RuntimeError("%s: the perceptual net must be a zest_networks.LPIPS, got %s" % (who, type(net).__name__))
+    return net
+
+
+def perceptual_loss(net, rgb_pred, rgb_gt, patch_size):
+    """The perceptual term of the static training step (train.py:626-632): LPIPS (net: a zest_networks.LPIPS) between
+    the rendered patches and the target's.  rgb_pred, rgb_gt: [..., R, 3] in [0, 1], R a multiple of patch_size^2, cut
+    into patches of patch_size x patch_size in their order as patch_terms cuts them and read in place; the reference's
+    `* 2 - 1` is applied in the kernel (normalize).  The gradient goes to rgb_pred only -> [B], one value per patch."""
+    who = "perceptual_loss"
+    net = _perceptual(who, net)
+    named = [("rgb_pred", rgb_pred, 3), ("rgb_gt", rgb_gt, 3)]
+    _check_shapes(who, named, 1, "[..., N_rays")
+    ps = int(patch_size)
+    if ps < zest_hip.LPIPS_MIN_SIDE:
+        raise RuntimeError("%s: patch_size %d < %d leaves a layer of the network without a pixel" % (who, ps, zest_hip.LPIPS_MIN_SIDE))
+    if rgb_pred.shape[-2] % (ps * ps):
+        raise RuntimeError("%s: %d rays are not a multiple of patch_size^2 = %d" % (who, rgb_pred.shape[-2], ps * ps))
+    _check_devices(who, named)
+    return net.forward_nhwc(rgb_pred.float().reshape(-1, ps, ps, 3), rgb_gt.detach().float().reshape(-1, ps, ps, 3),
+                            normalize=True).reshape(-1)
+
+
+def train_step_loss(results, hparams, adversarial=False, discriminator=None, perceptual=None):
     """The part of one static ("svs") training step that this package evaluates: MVSNeRFSystem.training_step
-    (train.py:587-760) without its class, its perceptual network and the discriminators other than GRAF's.
+    (train.py:587-760) without its class and the discriminators other than GRAF's.
     discriminator: None, or (adversarial only) a zest_networks.GRAFDiscriminator: the generator's adversarial term
     lambda_adv mean (D(rgb_map) - 1)^2 (lsgan; train.py:646-654) is added to the loss and logged as G_fake_loss.  Its
     gradient goes to rgb_map, and to the discriminator's weights unless they are frozen (Lightning's toggle_optimizer
     freezes them in this step: then no weight-gradient kernel runs).
+    perceptual: None (the default: the function does what it did without the argument and ignores
+    with_perceptual_loss), or a zest_networks.LPIPS.  With hparams.with_perceptual_loss set, perceptual_loss =
+    lambda_perc * LPIPS(rgb_map patch, target_s patch) (train.py:626-632) is logged, detached; with adversarial=True it
+    is added to the loss (train.py:694) and its gradient goes to rgb_map; with adversarial=False it is only logged and
+    evaluated without a graph, because the reference's plain total (train.py:744-748) leaves it out.  More than one
+    patch is refused: the reference's term is [B,1,1,1] there, its loss is no scalar and cannot be backpropagated.
     results: what the model returned; read are rgb_map [..., R, 3], target_s [..., R, 3], depth_map [..., R],
     weights [1, R, S] and t_vals (the last two only with_distortion_loss).  hparams (attributes or keys): patch_size,
     with_depth_loss_reg / lambda_depth_reg (total variation of the depth patches), with_depth_smoothness /
@@ -431,12 +465,15 @@ def train_step_loss(results, hparams, adversarial=False, discriminator=None):
           total.  That is what the reference trains with, so it is what this function returns.
       adversarial=True: the terms of the generator step (optimizer_idx 0, train.py:683-694) that need no network,
           l_rec mse + l_reg tv + l_smooth smooth + l_dist distortion, plus G_fake_loss where a discriminator is given
-          (else the caller's to add); the caller adds the feature-matching and the perceptual term.
-    hparams.train_sceneflow must be false (that step is train_sf_step_loss).  with_perceptual_loss, with_depth_loss_rec
-    and the depth discriminator are not evaluated here and are ignored: their terms are the caller's to add.
+          (else the caller's to add) and perceptual_loss where a perceptual net is given (else the caller's to add);
+          the caller adds the feature-matching term.  With both nets given this is the complete generator loss of
+          train.py:687-694 apart from the default-off terms below.
+    hparams.train_sceneflow must be false (that step is train_sf_step_loss).  with_depth_loss_rec and the depth
+    discriminator are not evaluated here and are ignored, as is with_perceptual_loss without a perceptual net: their
+    terms are the caller's to add.
     -> (loss with the graph, {name: logged value}) with the reference's names, weighted as it logs them: tv_depth_loss,
     depth_smooth_loss, distortion_loss (each where its flag is set), G_rec_loss (adversarial only), G_fake_loss (with a
-    discriminator) and train_PSNR =
+    discriminator), perceptual_loss (with a perceptual net and with_perceptual_loss) and train_PSNR =
     10 log10(1 / mse)."""
     hp = _hparams(hparams)
     if hp("train_sceneflow"):
@@ -447,6 +484,15 @@ def train_step_loss(results, hparams, adversarial=False, discriminator=None):
                                "(gan_type None) has no adversarial term")
         _discriminator("train_step_loss", discriminator)
         _lsgan("train_step_loss", hparams)
+    with_perc = perceptual is not None and bool(hp("with_perceptual_loss"))
+    if perceptual is not None:
+        _perceptual("train_step_loss", perceptual)
+        ps = int(hp("patch_size"))
+        if with_perc and torch.is_tensor(results["rgb_map"]) and results["rgb_map"].dim() >= 2 \
+                and results["rgb_map"].numel() // 3 > ps * ps:
+            raise RuntimeError("train_step_loss: %d rays are more than one patch of %d x %d: the reference's perceptual "
+                               "term is [B,1,1,1] then, its loss is no scalar and cannot be backpropagated"
+                               % (results["rgb_map"].numel() // 3, ps, ps))
     l_reg = float(hp("lambda_depth_reg")) if hp("with_depth_loss_reg") else 0.0
     l_smooth = float(hp("lambda_depth_smooth")) if hp("with_depth_smoothness") else 0.0
     l_dist = float(hp("lambda_distortion")) if hp("with_distortion_loss") else 0.0
@@ -471,5 +517,12 @@ def train_step_loss(results, hparams, adversarial=False, discriminator=None):
         g_fake = float(hp("lambda_adv")) * ((discriminator(results["rgb_map"]) - 1.0) ** 2).mean()
         logs["G_fake_loss"] = g_fake.detach()
         total = total + g_fake
+    if with_perc:
+        with torch.set_grad_enabled(adversarial and torch.is_grad_enabled()):
+            perc = float(hp("lambda_perc")) * perceptual_loss(perceptual, results["rgb_map"], results["target_s"],
+                                                              hp("patch_size")).sum()
+        logs["perceptual_loss"] = perc.detach()
+        if adversarial:
+            total = total + perc
     logs["train_PSNR"] = psnr
     return total, logs

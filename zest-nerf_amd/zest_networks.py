@@ -1013,3 +1013,131 @@ class GRAFDiscriminator(nn.Module):
         logits = zest_autograd.GrafDiscFn.apply(x, self.imsize, self.ndf, self.training, [m.weight_u for m in layers],
                                                 [m.weight_v for m in layers], *[m.weight_orig for m in layers])
         return logits.reshape(-1, 1, 1, 1)
+
+
+# ------------------------------------------------------------------------------------------ LPIPS (AlexNet)
+class _State(nn.Module):
+    """A module that only holds tensors under the names a state dict gives them."""
+
+    def __init__(self, params=(), buffers=(), children=()):
+        super().__init__()
+        for name, t in params:
+            self.register_parameter(name, nn.Parameter(t, requires_grad=False))
+        for name, t in buffers:
+            self.register_buffer(name, t)
+        for name, m in children:
+            self.add_module(name, m)
+
+    def __getitem__(self, name):
+        return self._modules[str(name)]
+
+
+class LPIPS(nn.Module):
+    """LPIPS v0.1 with the AlexNet backbone on the kernels of csrc/lpips.hip: the `lpips.LPIPS(net='alex')` of the
+    reference's training step (train.py:86, 626-632) and of its val_lpips / test_lpips metric, with that package's
+    state-dict keys - written from memory of the package, which is not available where this was built; KEYS below is
+    the one place that names them:
+        scaling_layer.shift, scaling_layer.scale [1,3,1,1]; net.slice1.0 / slice2.3 / slice3.6 / slice4.8 / slice5.10
+        .weight and .bias; lin0.model.1.weight .. lin4.model.1.weight [1,C,1,1].
+    The package also carries the lin layers a second time as lins.<k>.model.1.weight: load_state_dict accepts and
+    ignores them.  Every weight has requires_grad=False; the initial values are NOT the pretrained ones (they come from
+    a state dict: zest_dropin.install(perceptual=True) copies the package's).
+    forward(in0, in1, retPerLayer=False, normalize=False): [N,3,H,W], any H, W >= 31, any strides -> [N,1,1,1] (and the
+    five per-layer terms).  forward_nhwc takes [N,H,W,3] (channels-last patches, rays in patch order) without a permute
+    copy.  The gradient goes to in0 only: in1 is the target.  There is no torch path: CPU tensors raise.
+    Not built: the Dropout of the package's lin layers (active when Lightning puts the module in train mode; random, so
+    it cannot be pinned: this module evaluates the published metric whatever self.training is), spatial=True,
+    net='vgg' / 'squeeze', trainable lin layers, HIP-graph capture, bf16."""
+
+    CONVS = ((3, 64, 11), (64, 192, 5), (192, 384, 3), (384, 256, 3), (256, 256, 3))
+    SLICE_INDEX = (0, 3, 6, 8, 10)                           # the convolution's index in torchvision's alexnet.features
+    SHIFT, SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+    # state-dict keys, per layer k = 0..4: (weight, bias, lin); the duplicates that are dropped on load start with DROP
+    KEYS = tuple(("net.slice%d.%d.weight" % (k + 1, i), "net.slice%d.%d.bias" % (k + 1, i), "lin%d.model.1.weight" % k)
+                 for k, i in enumerate(SLICE_INDEX))
+    SHIFT_KEY, SCALE_KEY, DROP = "scaling_layer.shift", "scaling_layer.scale", "lins."
+
+    def __init__(self, pretrained=True, net='alex', version='0.1', lpips=True, spatial=False, pnet_rand=False, pnet_tune=False,
+                 use_dropout=True, model_path=None, eval_mode=True, verbose=False):
+        super().__init__()
+        if net not in ('alex', 'alexnet'):
+            raise NotImplementedError("LPIPS: net=%r; only the AlexNet backbone ('alex') has kernels (the reference's "
+                                      "train.py uses no other)" % (net,))
+        if spatial:
+            raise NotImplementedError("LPIPS: spatial=True returns a map per pixel; only the spatial mean is built")
+        if version != '0.1' or not lpips or pnet_tune:
+            raise NotImplementedError("LPIPS: version %r, lpips=%r, pnet_tune=%r; only v0.1 with frozen linear layers is built"
+                                      % (version, lpips, pnet_tune))
+        self.scaling_layer = _State(buffers=[("shift", torch.tensor(self.SHIFT).view(1, 3, 1, 1)),
+                                             ("scale", torch.tensor(self.SCALE).view(1, 3, 1, 1))])
+        slices = []
+        for k, ((cin, cout, ks), i) in enumerate(zip(self.CONVS, self.SLICE_INDEX)):
+            w = torch.empty(cout, cin, ks, ks)
+            nn.init.kaiming_uniform_(w, a=5 ** 0.5)
+            conv = _State(params=[("weight", w), ("bias", torch.zeros(cout))])
+            slices.append(("slice%d" % (k + 1), _State(children=[(str(i), conv)])))
+            lin = _State(params=[("weight", torch.full((1, cout, 1, 1), 1.0 / cout))])
+            self.add_module("lin%d" % k, _State(children=[("model", _State(children=[("1", lin)]))]))
+        self.net = _State(children=slices)
+        self._packed = None
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith(self.DROP)}, strict=strict, **kw)
+
+    def _tensors(self):
+        """-> (weights, biases, lins, shift, scale) in the order of the layers."""
+        sd = dict(self.named_parameters())
+        sd.update(self.named_buffers())
+        cols = list(zip(*[[sd[name] for name in keys] for keys in self.KEYS]))
+        return list(cols[0]), list(cols[1]), list(cols[2]), sd[self.SHIFT_KEY], sd[self.SCALE_KEY]
+
+    def packed(self):
+        """The packed copy of the weight state, rebuilt when a weight's device, storage or version counter moves (an
+        in-place change bumps `_version`; a cache compared by identity would miss it)."""
+        w, b, lin, shift, scale = self._tensors()
+        every = w + b + lin + [shift, scale]
+        for t in every:
+            if not t.is_cuda:
+                raise RuntimeError("LPIPS: a weight is on %s; this path runs only on a HIP device" % (t.device,))
+        key = tuple((str(t.device), t.data_ptr(), t._version) for t in every)
+        if self._packed is None or self._packed[0] != key:
+            c = lambda t: t.detach().float().contiguous()   # noqa: E731
+            self._packed = (key, zest_hip.lpips_pack([c(t) for t in w], [c(t) for t in b], [c(t) for t in lin], c(shift), c(scale)))
+        return self._packed[1]
+
+    def _run(self, in0, in1, retPerLayer, normalize):
+        import zest_autograd
+        who = "LPIPS"
+        for name, t in (("in0", in0), ("in1", in1)):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
+                raise RuntimeError("%s: %s must be a tensor [N, 3, H, W], got %s"
+                                   % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if in0.shape != in1.shape:
+            raise RuntimeError("%s: in1 %s does not match in0 %s" % (who, tuple(in1.shape), tuple(in0.shape)))
+        if in0.shape[0] < 1 or min(in0.shape[2:]) < zest_hip.LPIPS_MIN_SIDE:
+            raise RuntimeError("%s: %s is an empty batch or a frame below %d x %d, the smallest with a pixel in every layer"
+                               % (who, tuple(in0.shape), zest_hip.LPIPS_MIN_SIDE, zest_hip.LPIPS_MIN_SIDE))
+        for name, t in (("in0", in0), ("in1", in1)):
+            if not t.is_cuda:
+                raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device" % (who, name, t.device))
+        if in1.device != in0.device:
+            raise RuntimeError("%s: in1 is on %s, in0 on %s" % (who, in1.device, in0.device))
+        packed = self.packed()
+        if packed.device != in0.device:
+            raise RuntimeError("%s: the weights are on %s, in0 on %s" % (who, packed.device, in0.device))
+        res = zest_autograd.LpipsFn.apply(in0.float(), in1.detach().float(), packed, bool(normalize), torch.is_grad_enabled())
+        val = res[:, 0].reshape(-1, 1, 1, 1)
+        if retPerLayer:
+            return val, [res[:, 1 + k].reshape(-1, 1, 1, 1) for k in range(zest_hip.LPIPS_LAYERS)]
+        return val
+
+    def forward(self, in0, in1, retPerLayer=False, normalize=False):
+        return self._run(in0, in1, retPerLayer, normalize)
+
+    def forward_nhwc(self, in0, in1, retPerLayer=False, normalize=False):
+        """forward for in0, in1 [N,H,W,3]: channels-last images, or rays reshaped to patches; read in place."""
+        for name, t in (("in0", in0), ("in1", in1)):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[-1] != 3:
+                raise RuntimeError("LPIPS: %s must be a tensor [N, H, W, 3], got %s"
+                                   % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        return self._run(in0.permute(0, 3, 1, 2), in1.permute(0, 3, 1, 2), retPerLayer, normalize)

@@ -467,6 +467,38 @@ int zest_lpips_fwd(const float *in0, const long long *stride0, const float *in1,
 int zest_lpips_bwd(const float *packed, const float *saved, const float *g, int N, int H, int W, int normalize,
                    float *work, float *g_in0, const long long *gstride, void *stream);
 
+/* Image metrics of a rendered frame: mse, psnr and ssim of the reference's validation and test steps
+ * (train.py:784-800, 904-915, 992-1008: kornia.metrics.psnr / ssim of release 0.6.9, restated in
+ * tests/metrics_cases.py), in two launches: one workgroup per tile forms the windowed statistics, one
+ * workgroup adds the tiles' partial sums in a fixed order.
+ *   p    = clamp(pred, 0, 1) if clamp_pred, else pred; the target is never clamped
+ *   mse  = mean (p - t)^2 over the N C H W elements
+ *   psnr = 10 log10(max_val^2 / mse), +inf for mse == 0
+ *   window: g[i] = exp(-(i - ws/2)^2 / (2 1.5^2)), i = 0 .. ws-1, normalised to sum 1; 2-D window g g^T,
+ *     per plane (channels do not mix); padding ws/2 on every side by reflection without repeating the edge
+ *     (index -1 -> 1, H -> H-2)
+ *   mu1 = G*p, mu2 = G*t, s1 = G*(p p) - mu1^2, s2 = G*(t t) - mu2^2, s12 = G*(p t) - mu1 mu2
+ *   C1 = (0.01 max_val)^2, C2 = (0.03 max_val)^2
+ *   map  = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2) + 1e-12)
+ *   ssim = mean of the map over the N C H W elements
+ * pred, target: [N,C,H,W] fp32 addressed through strides in elements (stride[0..3] of n, c, h, w), read in
+ * place: NCHW, channels-last, ray-ordered frames and crops alike.  ws: odd, 3 .. 11.
+ * zest_image_metrics_tile: host only: the tile (rows, columns) a workgroup of the first launch owns.
+ * zest_image_metrics_work_bytes: host only: bytes of `work` for a shape (0 and an error text for a bad one).
+ * zest_image_metrics writes result [ZEST_IMG_COLS]: 0 mse, 1 psnr, 2 ssim, 3 sum (p - t)^2, 4 sum of the
+ *   map; and, where not NULL, ssim_map [N,C,H,W] and abs_err = |p - t| [N,C,H,W], both contiguous, every
+ *   element once.  work: work_bytes >= zest_image_metrics_work_bytes(N, C, H, W) bytes of device memory.
+ * No float atomics: two calls on the same inputs are bit-identical, and so are two layouts of one image.
+ * Errors: N, C, H or W < 1; ws even or outside 3 .. 11; H or W <= ws/2; NULL pred, target, stride table,
+ * result or work; work_bytes too small; max_val <= 0. */
+#define ZEST_IMG_COLS 5
+int zest_image_metrics_tile(int *th, int *tw);
+size_t zest_image_metrics_work_bytes(int N, int C, int H, int W);
+int zest_image_metrics(const float *pred, const long long *pred_stride, const float *target,
+                       const long long *target_stride, int N, int C, int H, int W, int ws, int clamp_pred,
+                       float max_val, float *result, float *ssim_map, float *abs_err, void *work,
+                       size_t work_bytes, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

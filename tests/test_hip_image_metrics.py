@@ -1,0 +1,228 @@
+"""GPU: csrc/image_metrics.hip (mse, psnr, ssim of a frame in two launches) against the float64 restatement of
+tests/metrics_cases.py.
+
+Bounds: the project's own (test_hip_ops.ATOL, RTOL = 1e-4 + 1e-3 |want|) on mse and ssim, on psnr relative to its value,
+and PER PIXEL on the SSIM map and the error map; no element is excused (the function has no kinks).  The fp32 torch
+composition on a CPU, which takes E[x^2] - mu^2 as it stands, comes within 0.57 of the per-pixel bound on the near-flat
+case, within 0.33 on the other smooth ones and within 0.01 on the noisy one, and its means within 1e-6: the bound is
+reachable.  The kernel takes the moments about a pivot and came within 0.14 of it on every case (each test prints its
+figures).  Layouts, repeated calls and the optional outputs are compared bit for bit: the kernel orders every sum
+itself, and a layout changes addresses only.
+"""
+import numpy as np
+import pytest
+import torch
+
+import lpips_cases as lc
+import metrics_cases as mc
+from test_hip_ops import ATOL, RTOL
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _dev(a):
+    return torch.from_numpy(np.array(a)).to(DEV)
+
+
+def _close(got, want, what):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    err = np.abs(got - want)
+    bound = ATOL + RTOL * np.abs(want)
+    print("%s: worst error / bound = %.4f" % (what, float((err / bound).max())))
+    assert (err <= bound).all(), (what, float((err / bound).max()))
+
+
+def _check_case(case, ws=5):
+    import zest_metrics
+    pred, target = mc.images(*case)
+    want = mc.restated(*case, ws=ws)
+    out = zest_metrics.image_metrics(_dev(pred), _dev(target), window=ws, clamp_pred=case[5], want_map=True, want_err=True)
+    _close(out["mse"].item(), want["mse"], "mse")
+    _close(out["ssim"].item(), want["ssim"], "ssim")
+    psnr = out["psnr"].item()
+    print("psnr: got %.6f want %.6f" % (psnr, want["psnr"]))
+    assert abs(psnr - want["psnr"]) <= RTOL * abs(want["psnr"])
+    assert out["ssim_map"].shape == pred.shape and out["abs_err"].shape == pred.shape
+    _close(out["ssim_map"].cpu().numpy(), want["map"], "ssim map")
+    _close(out["abs_err"].cpu().numpy(), want["err"], "error map")
+    return out
+
+
+@pytest.mark.parametrize("case", mc.SMALL_CASES, ids=lambda c: "%dx%dx%dx%d-amp%g" % c[:5])
+def test_small_cases(case):
+    _check_case(case)
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_either_side_of_the_tile(which):
+    import zest_hip
+    _check_case(mc.tile_cases(*zest_hip.image_metrics_tile())[which])
+
+
+@pytest.mark.parametrize("ws", [3, 7, 11])
+def test_windows(ws):
+    _check_case(mc.WINDOW_CASE, ws=ws)
+
+
+def test_smallest_frame_of_the_widest_window():
+    """ws = 11 pads by 5: H = 6 is accepted (and right), H = 5 raises."""
+    import zest_metrics
+    _check_case((1, 1, 6, 14, 0.3, True), ws=11)
+    x = torch.zeros(1, 1, 5, 14, device=DEV)
+    with pytest.raises(RuntimeError, match="reflect padding"):
+        zest_metrics.image_metrics(x, x, window=11)
+    with pytest.raises(RuntimeError, match="reflect padding"):
+        zest_metrics.image_metrics(x.transpose(2, 3), x.transpose(2, 3), window=11)
+    for bad in (4, 13, 1):
+        with pytest.raises(RuntimeError, match="odd size in 3..11"):
+            zest_metrics.image_metrics(torch.zeros(1, 1, 20, 20, device=DEV), torch.zeros(1, 1, 20, 20, device=DEV), window=bad)
+
+
+def test_c_abi_call_with_the_exact_work_size(hip):
+    """The entry called directly with exactly zest_image_metrics_work_bytes of work and NULL maps (its refusals need no
+    GPU: tests/test_metrics_cpu.py); one byte less is refused before any launch."""
+    import ctypes as C
+    import zest_hip
+    case = (1, 3, 17, 65, 0.05, True)
+    pred, target = _pair(case)
+    want = mc.restated(*case)
+    need = hip.zest_image_metrics_work_bytes(*case[:4])
+    assert need == 3 * 2 * 2 * 8
+    res = torch.full((zest_hip.IMG_COLS,), -1.0, device=DEV)
+    work = torch.empty(need, device=DEV, dtype=torch.uint8)
+    st = (C.c_longlong * 4)(*pred.stride())
+    args = (pred.data_ptr(), st, target.data_ptr(), st, 1, 3, 17, 65, 5, 1, 1.0, res.data_ptr(), None, None, work.data_ptr())
+    assert hip.zest_image_metrics(*args, need - 1, None) != 0 and b"zest_image_metrics: work buffer" in hip.zest_last_error()
+    assert hip.zest_image_metrics(*args, need, None) == 0
+    torch.cuda.synchronize()
+    got = res.cpu().numpy().astype(np.float64)
+    _close(got[0], want["mse"], "mse")
+    _close(got[2], want["ssim"], "ssim")
+    assert abs(got[1] - want["psnr"]) <= RTOL * abs(want["psnr"])
+    # the raw sums the means come from
+    count = float(np.prod(case[:4]))
+    assert abs(got[3] / count - got[0]) <= 1e-6 * got[0] and abs(got[4] / count - got[2]) <= 1e-6 * got[2]
+
+
+def _pair(case=(1, 3, 37, 50, 0.6, True)):
+    pred, target = mc.images(*case)
+    return _dev(pred), _dev(target)
+
+
+def _all(pred, target, **kw):
+    import zest_hip
+    res, smap, err = zest_hip.image_metrics(pred, target, clamp_pred=True, want_map=True, want_err=True, **kw)
+    return res.cpu().numpy(), smap.cpu().numpy(), err.cpu().numpy()
+
+
+def _same(a, b):
+    return all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(a, b))
+
+
+def test_layouts_are_bit_identical():
+    pred, target = _pair()
+    N, C, H, W = pred.shape
+    base = _all(pred, target)
+    # the prediction as a ray-ordered [H*W, 3] view
+    rays = pred[0].permute(1, 2, 0).reshape(H * W, 3).contiguous()
+    view = rays.as_strided((1, 3, H, W), (0, 1, 3 * W, 3))
+    assert view.data_ptr() == rays.data_ptr() and torch.equal(view, pred)
+    assert _same(base, _all(view, target))
+    # the target channels-last
+    cl = target.contiguous(memory_format=torch.channels_last)
+    assert cl.stride() != target.stride()
+    assert _same(base, _all(pred, cl))
+    # a target sliced out of [V,3,H,W]
+    stack = torch.rand(4, 3, H, W, device=DEV)
+    stack[2] = target[0]
+    assert _same(base, _all(pred, stack[2:3]))
+    # both as non-contiguous crops of larger tensors
+    bigp, bigt = torch.rand(1, 3, H + 7, W + 9, device=DEV), torch.rand(2, 4, H + 3, W + 5, device=DEV)
+    bigp[:, :, 3:3 + H, 4:4 + W] = pred
+    bigt[1:2, 1:4, 2:2 + H, 5:5 + W] = target
+    cp, ct = bigp[:, :, 3:3 + H, 4:4 + W], bigt[1:2, 1:4, 2:2 + H, 5:5 + W]
+    assert not cp.is_contiguous() and not ct.is_contiguous()
+    assert _same(base, _all(cp, ct))
+
+
+def test_validation_metrics_from_ragged_chunks():
+    import zest_metrics
+    import zest_networks
+    H, W, sizes = mc.RAGGED
+    assert sum(sizes) == H * W
+    pred, target = _pair((1, 3, H, W, 0.05, True))
+    rays = pred[0].permute(1, 2, 0).reshape(H * W, 3).contiguous()
+    chunks = list(torch.split(rays, list(sizes)))
+    want = zest_metrics.image_metrics(pred, target, window=5, clamp_pred=True)
+    for rgbs, tgt in ((chunks, target), (rays, target[0]), (chunks, target.contiguous(memory_format=torch.channels_last))):
+        got = zest_metrics.validation_metrics(rgbs, tgt, H, W)
+        assert sorted(got) == ["val_loss", "val_psnr", "val_ssim"]
+        for a, b in (("val_loss", "mse"), ("val_psnr", "psnr"), ("val_ssim", "ssim")):
+            assert got[a].dim() == 0 and got[a].item() == want[b].item(), (a, got[a].item(), want[b].item())
+    ref = mc.restated(1, 3, H, W, 0.05, True)
+    _close(want["ssim"].item(), ref["ssim"], "ssim")
+    _close(want["mse"].item(), ref["mse"], "mse")
+    P = zest_networks.LPIPS()
+    P.load_state_dict({k: torch.from_numpy(v) for k, v in lc.state(lc.DEFAULT_SEED).items()}, strict=True)
+    P = P.to(DEV).eval()
+    got = zest_metrics.validation_metrics(chunks, target, H, W, perceptual=P)
+    assert sorted(got) == ["val_loss", "val_lpips", "val_psnr", "val_ssim"]
+    with torch.no_grad():
+        lp = P(pred.clamp(0.0, 1.0), target)
+    assert got["val_lpips"].shape == lp.shape and torch.equal(got["val_lpips"], lp) and float(lp) > 0
+    assert got["val_ssim"].item() == want["ssim"].item()
+
+
+def test_two_calls_are_bit_identical_and_maps_do_not_move_the_scalars():
+    import zest_hip
+    pred, target = _pair()
+    a, b = _all(pred, target), _all(pred, target)
+    assert _same(a, b)
+    for want_map, want_err in ((False, False), (True, False), (False, True)):
+        res, smap, err = zest_hip.image_metrics(pred, target, clamp_pred=True, want_map=want_map, want_err=want_err)
+        assert (smap is not None) == want_map and (err is not None) == want_err
+        assert _same((a[0],), (res.cpu().numpy(),))
+
+
+def test_kornia_signatures():
+    """psnr -> a 0-d tensor without a clamp; ssim -> the map [B,C,H,W]."""
+    import zest_metrics
+    case = (2, 3, 5, 4, 0.3, False)
+    pred, target = _pair(case)
+    want = mc.restated(*case)
+    ps = zest_metrics.psnr(pred, target, 1)
+    assert ps.dim() == 0 and abs(ps.item() - want["psnr"]) <= RTOL * abs(want["psnr"])
+    sm = zest_metrics.ssim(pred, target, 5)
+    assert sm.shape == pred.shape
+    _close(sm.cpu().numpy(), want["map"], "ssim map")
+    _close(sm.mean().item(), want["ssim"], "ssim")
+    # any rank, as kornia takes: the [1,N_rays,3] colours of a training step, viewed without a copy; six dimensions
+    rays, rays_t = pred.permute(0, 2, 3, 1).reshape(1, -1, 3), target.permute(0, 2, 3, 1).reshape(1, -1, 3)
+    for a, b in ((rays, rays_t), (rays[0], rays_t[0]), (pred.reshape(2, 3, 1, 1, 5, 4), target.reshape(2, 3, 1, 1, 5, 4))):
+        assert abs(zest_metrics.psnr(a, b, 1).item() - want["psnr"]) <= RTOL * abs(want["psnr"])
+    # max_val scales C1, C2 and the psnr
+    p2 = zest_metrics.psnr(pred, target, 2.0)
+    assert abs(p2.item() - (want["psnr"] + 20.0 * np.log10(2.0))) <= RTOL * abs(p2.item())
+    want2 = mc.restated(*case, ws=5, max_val=2.0)
+    _close(zest_metrics.ssim(pred, target, 5, max_val=2.0).cpu().numpy(), want2["map"], "ssim map, max_val 2")
+
+
+def test_identical_inputs():
+    import zest_metrics
+    _, target = _pair()
+    out = zest_metrics.image_metrics(target, target.clone(), want_map=True, want_err=True)
+    assert out["mse"].item() == 0.0 and out["psnr"].item() == float("inf") and abs(out["ssim"].item() - 1.0) <= 1e-5
+    assert float(out["abs_err"].abs().max()) == 0.0
+
+
+def test_production_frame():
+    """1 x 3 x 288 x 512 once, scalars only."""
+    import zest_metrics
+    pred, target = mc.images(*mc.PRODUCTION)
+    want = mc.restated(*mc.PRODUCTION)
+    out = zest_metrics.image_metrics(_dev(pred), _dev(target), window=5, clamp_pred=True)
+    assert sorted(out) == ["mse", "psnr", "ssim"]
+    _close(out["mse"].item(), want["mse"], "mse")
+    _close(out["ssim"].item(), want["ssim"], "ssim")
+    assert abs(out["psnr"].item() - want["psnr"]) <= RTOL * abs(want["psnr"])

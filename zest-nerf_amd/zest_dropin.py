@@ -7,7 +7,7 @@ The reference binds its hot path by module attribute: `from renderer import rend
 named `networks`, `utils`, `renderer` or `losses` - it shadows nothing.  `install()` imports the
 CALLER'S OWN modules of those names and rebinds, inside them, only the names of the rendering
 path to the HIP implementations (zest_renderer, zest_networks, zest_utils, zest_losses); every
-other name - discriminators (GRAF's can be opted in, below, and so can the `lpips` package's network), visualisation helpers, image-space losses, data loaders - stays the
+other name - discriminators (GRAF's can be opted in, below, and so can the `lpips` package's network and kornia's `psnr` / `ssim`), visualisation helpers, image-space losses, data loaders - stays the
 caller's.  A script that runs afterwards (`from networks import ...`) picks the rebound names up.
 
     import zest_dropin; zest_dropin.install()           # then: import train
@@ -25,7 +25,7 @@ import sys
 import types
 
 __all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "DISCRIMINATOR_NAMES",
-           "PERCEPTUAL_NAMES", "main"]
+           "PERCEPTUAL_NAMES", "METRIC_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -51,6 +51,9 @@ DISCRIMINATOR_NAMES = ("GRAFDiscriminator",)
 # opt-in (install(perceptual=True) / ZEST_DROPIN_PERCEPTUAL=1): `lpips.LPIPS` of the caller's own `lpips` package
 # becomes a factory that returns a zest_networks.LPIPS (csrc/lpips.hip) holding the package's pretrained weights
 PERCEPTUAL_NAMES = ("LPIPS",)
+# opt-in (install(metrics=True) / ZEST_DROPIN_METRICS=1): `psnr` and `ssim` of the caller's own `kornia.metrics` become
+# zest_metrics.psnr / ssim (csrc/image_metrics.hip), before the caller's script does `from kornia.metrics import psnr, ssim`
+METRIC_NAMES = ("psnr", "ssim")
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -89,7 +92,7 @@ def _lpips_factory(package_cls):
 
 
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False):
+            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False, metrics=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
@@ -99,6 +102,8 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
     perceptual: also rebind `LPIPS` in the caller's `lpips` package (imported here; ImportError if it is missing) to a
     factory that lets the package build its pretrained module and returns a zest_networks.LPIPS with that state (off
     by default: `lpips.LPIPS` stays the package's).
+    metrics: also rebind `psnr` and `ssim` in the caller's `kornia.metrics` (imported here; ImportError if it is missing)
+    to zest_metrics.psnr / ssim (off by default: they stay kornia's).
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -139,6 +144,12 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
         for n in PERCEPTUAL_NAMES:
             _bind(package, n, _lpips_factory(getattr(package, n)))
         done["lpips"] = sorted(PERCEPTUAL_NAMES)
+    if metrics:
+        package = importlib.import_module("kornia.metrics")
+        zest = importlib.import_module("zest_metrics")
+        for n in METRIC_NAMES:
+            _bind(package, n, getattr(zest, n))
+        done["kornia.metrics"] = sorted(METRIC_NAMES)
     return done
 
 
@@ -161,13 +172,15 @@ def main(argv=None):
               "regularisers (compute_sf_smooth_loss, compute_sf_lke_loss), ZEST_DROPIN_PATCH_LOSSES=1 the patch "
               "regularisers of the static step (total_variation_loss, get_disparity_smoothness), ZEST_DROPIN_DISCRIMINATOR=1 "
               "the GRAF patch discriminator (networks.GRAFDiscriminator), ZEST_DROPIN_PERCEPTUAL=1 the LPIPS network "
-              "(lpips.LPIPS, AlexNet backbone)")
+              "(lpips.LPIPS, AlexNet backbone), ZEST_DROPIN_METRICS=1 the image metrics of the validation and test steps "
+              "(kornia.metrics.psnr, kornia.metrics.ssim)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
     install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
             patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1",
             discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1",
-            perceptual=os.environ.get("ZEST_DROPIN_PERCEPTUAL", "") == "1")
+            perceptual=os.environ.get("ZEST_DROPIN_PERCEPTUAL", "") == "1",
+            metrics=os.environ.get("ZEST_DROPIN_METRICS", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

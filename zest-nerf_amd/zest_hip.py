@@ -94,6 +94,10 @@ _SIGS = {
     "zest_lpips_pack": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _vp]),
     "zest_lpips_fwd": (_i, [_vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "zest_lpips_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong), _vp]),
+    "zest_image_metrics_tile": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "zest_image_metrics_work_bytes": (_sz, [_i, _i, _i, _i]),
+    "zest_image_metrics": (_i, [_vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _i, _i, _i, _i, _i, _i, _f,
+                                _vp, _vp, _vp, _vp, _sz, _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -746,6 +750,68 @@ def lpips_saved_views(saved, N, H, W):
         n = 2 * N * L["h"] * L["w"] * L["channels"]
         out.append(saved[L["act"]:L["act"] + n].view(2 * N, L["h"], L["w"], L["channels"]))
     return out
+
+
+# ------------------------------------------------------------------------ image metrics (csrc/image_metrics.hip)
+IMG_COLS = 5                      # result columns: mse, psnr, ssim, sum (p - t)^2, sum of the SSIM map
+IMG_WINDOWS = (3, 5, 7, 9, 11)
+_img_work = {}                    # (device, bytes) -> the partial-sum buffer of image_metrics
+
+
+def image_metrics_tile():
+    """-> (rows, columns) of the tile a workgroup of csrc/image_metrics.hip owns (no GPU call; for the tests, which
+    choose their sizes either side of it)."""
+    th, tw = _i(), _i()
+    _check(lib().zest_image_metrics_tile(C.byref(th), C.byref(tw)), "zest_image_metrics_tile")
+    return th.value, tw.value
+
+
+def _metric_image(who, name, t, like=None):
+    """An fp32 tensor [N,C,H,W] of ANY strides (it is read in place) -> (tensor, its strides as a C array)."""
+    if not torch.is_tensor(t) or t.dim() != 4 or min(t.shape) < 1:
+        raise RuntimeError("zest_hip: %s: %s must be a non-empty tensor [N, C, H, W], got %s"
+                           % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if like is not None and t.shape != like.shape:
+        raise RuntimeError("zest_hip: %s: %s %s does not match pred %s" % (who, name, tuple(t.shape), tuple(like.shape)))
+    if not t.is_cuda:
+        raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+    if like is not None and t.device != like.device:
+        raise RuntimeError("zest_hip: %s: %s is on %s, pred on %s" % (who, name, t.device, like.device))
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t, (C.c_longlong * 4)(*t.stride())
+
+
+def image_metrics(pred, target, window=5, clamp_pred=False, max_val=1.0, want_map=False, want_err=False):
+    """MSE, PSNR and SSIM of pred against target, [N,C,H,W] fp32 of any strides (read in place, no copy), in two
+    launches -> (result [IMG_COLS]: mse, psnr, ssim over the whole batch and the two raw sums; the SSIM map [N,C,H,W] or
+    None; |p - t| [N,C,H,W] or None), p = clamp(pred, 0, 1) if clamp_pred.  window: odd, 3 .. 11, H and W above
+    window // 2 (reflect padding).  The buffer of partial sums is kept per (device, size): calls that share it belong on
+    one stream."""
+    who = "image_metrics"
+    pred, ps = _metric_image(who, "pred", pred)
+    target, ts = _metric_image(who, "target", target, pred)
+    N, Cc, H, W = pred.shape
+    window = int(window)
+    if window not in IMG_WINDOWS:
+        raise RuntimeError("zest_hip: %s: window %d is not an odd size in 3..11" % (who, window))
+    if min(H, W) <= window // 2:
+        raise RuntimeError("zest_hip: %s: a %d x %d frame does not exceed the reflect padding %d of window %d"
+                           % (who, H, W, window // 2, window))
+    L, dev = lib(), pred.device
+    need = L.zest_image_metrics_work_bytes(N, Cc, H, W)
+    if need == 0:
+        _check(1, "zest_image_metrics_work_bytes")
+    work = _img_work.get((dev, need))
+    if work is None:
+        work = _img_work[(dev, need)] = torch.empty(need, device=dev, dtype=torch.uint8)
+    result = torch.empty(IMG_COLS, device=dev, dtype=torch.float32)
+    ssim_map = torch.empty(N, Cc, H, W, device=dev, dtype=torch.float32) if want_map else None
+    abs_err = torch.empty(N, Cc, H, W, device=dev, dtype=torch.float32) if want_err else None
+    _check(L.zest_image_metrics(_ptr(pred), ps, _ptr(target), ts, N, Cc, H, W, window, int(bool(clamp_pred)), float(max_val),
+                                _ptr(result), _ptr(ssim_map), _ptr(abs_err), _ptr(work), need, _stream(pred)),
+           "zest_image_metrics")
+    return result, ssim_map, abs_err
 
 
 def nchw_to_nhwc(x):

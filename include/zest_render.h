@@ -499,6 +499,55 @@ int zest_image_metrics(const float *pred, const long long *pred_stride, const fl
                        float max_val, float *result, float *ssim_map, float *abs_err, void *work,
                        size_t work_bytes, void *stream);
 
+/* Multi-tensor Adam with the global-norm gradient clip applied in the update (reference train.py:265-301:
+ * torch.optim.Adam; train.py:1324-1335: Trainer(gradient_clip_val=1)).  fp32, one device.  Per element,
+ * torch's arithmetic for amsgrad=False, weight_decay=0, maximize=False:
+ *   g' = g coef;  m = m + (g' - m)(1 - b1);  v = b2 v + (1 - b2) g'^2
+ *   p = p - step_size m / (sqrt(v) rbc2 + eps)
+ *   coef = min(1, max_norm / (norm + 1e-6)) with the clip on, norm the 2-norm of all gradients of the
+ *     step; 1 with it off.  A NaN norm gives a NaN coefficient.
+ * The flat element space of the tensors is cut into chunks of zest_adam_chunk() elements (a multiple of
+ * 4) that never span two tensors; workgroups stride over the chunks, offsets are 64-bit.  16-byte loads
+ * and stores where the chunk start of all four arrays is 16-byte aligned, 4-byte ones otherwise; both
+ * visit the elements in the same order.
+ * zest_adam_chunk, zest_adam_max_tensors, zest_adam_max_slots: host only: elements of a chunk; tensors and
+ *   rows of scalars that one launch's argument block holds.
+ * zest_adam_plan: host only, no GPU call: sizes [n_tensors] (elements; 0 gives no chunk) -> the number of
+ *   chunks, and, where the two arrays are not NULL, chunk_tensor[k], chunk_offset[k] (elements into the
+ *   tensor) for each chunk in order; chunk k covers min(zest_adam_chunk(), sizes[t] - offset) elements.
+ *   -1 and an error text for a negative size or count, one array without the other, or more chunks than
+ *   `capacity`.
+ * zest_adam_work_bytes: host only: bytes of `work` for a number of chunks (0 and an error text if < 0).
+ * zest_adam_step: tensors: DEVICE table [n][ZEST_ADAM_TENSOR_COLS] of 64-bit values per tensor: address
+ *   of p, of exp_avg, of exp_avg_sq, element count (> 0), row of its scalars within its launch.
+ *   chunk_tensor, chunk_offset: DEVICE copies of zest_adam_plan's arrays for those sizes.
+ *   The step is cut into n_launches consecutive ranges, launch l covering the tensors
+ *   [launch_tensor[l], launch_tensor[l+1]) (at most zest_adam_max_tensors()) and the chunks
+ *   [launch_chunk[l], launch_chunk[l+1]) (HOST arrays of n_launches + 1 bounds starting at 0).
+ *   grads: HOST array of one device address per tensor; it travels in the launches' argument blocks and
+ *   is only read.  scalars: HOST [n_launches][zest_adam_max_slots()][ZEST_ADAM_SCALARS], computed by the
+ *   caller in double: 0 step_size = lr / (1 - b1^t), 1 rbc2 = 1 / sqrt(1 - b2^t), 2 eps, 3 1 - b1, 4 b2,
+ *   5 1 - b2 (passed beside b2: 1 - (float)b2 is 3e-5 off 1 - b2 at b2 = 0.999).
+ *   clip == 0: n_launches launches (the update).  clip != 0: 2 n_launches: first one fp32 sum of squares
+ *   per chunk into `work` (work_bytes >= zest_adam_work_bytes(chunks)), then the update, each workgroup of
+ *   which adds all of them in double in one fixed order; the norm is written to norm_out[0] (device).
+ * No float atomics: two calls on equal inputs are bit-identical.  n_launches == 0 does nothing.
+ * Errors: NULL tables, bounds, grads or scalars; bounds that do not start at 0; a launch without tensors
+ * or chunks or with more tensors than fit; a NULL gradient; with the clip on, NULL work or norm_out,
+ * work_bytes too small, max_norm negative or not finite. */
+#define ZEST_ADAM_TENSOR_COLS 5
+#define ZEST_ADAM_SCALARS 6
+int zest_adam_chunk(void);
+int zest_adam_max_tensors(void);
+int zest_adam_max_slots(void);
+long long zest_adam_plan(const long long *sizes, int n_tensors, int *chunk_tensor, long long *chunk_offset,
+                         long long capacity);
+size_t zest_adam_work_bytes(long long n_chunks);
+int zest_adam_step(const long long *tensors, const int *chunk_tensor, const long long *chunk_offset, int n_launches,
+                   const int *launch_tensor, const long long *launch_chunk, const void *const *grads,
+                   const float *scalars, int clip, float max_norm, void *work, size_t work_bytes,
+                   float *norm_out, void *stream);
+
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */
 int zest_volume_lookup_fwd(const float *vol_cl, int D, int H, int W, const float *ndc, int M,

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""The parameter update of one training step (reference train.py:265-301, 1324-1335: Adam under gradient_clip_val=1) on
+two parameter sets, the generator that tools/bench_generator_train.py builds (plus a `time_codes` group at lr * 10) and the
+ndf=64 GRAF discriminator, with fixed random gradients, three ways, each with and without the global-norm clip at 1:
+
+  torch        torch.optim.Adam as the reference builds it (the foreach implementation on a device), preceded by
+               torch.nn.utils.clip_grad_norm_ with the clip: what the reference runs; measured twice (.., torch_again)
+               for the spread
+  fused        torch.optim.Adam(fused=True), preceded by clip_grad_norm_ with the clip
+  hip          zest_optim.Adam (csrc/optim.hip), the clip inside the step (max_grad_norm=1)
+
+Every variant owns a copy of the parameters and is warmed up; then the variants alternate in blocks of synchronised
+iterations (host clock around the call + device synchronise), so drift of the machine lands on all of them alike.  The
+kernel count of one call comes from torch.profiler, in a pass of its own after the timing.  A gain over the reference's
+composition is stated only where it exceeds the spread of its two measurements; no time is fixed in advance.
+clip_grad_norm_ scales the gradients in place, so torch's gradients shrink to norm 1 in the first call and are multiplied
+by 1 from then on: the work per call does not change.
+
+    python tools/bench_optimizer.py [--iters 400] [--out profiles/optimizer_step.json]
+    python tools/bench_optimizer.py --loop 200       # only zest_optim.Adam with the clip, for a kernel-trace profiler run
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests"), ROOT):
+    sys.path.insert(0, p)
+import zest_optim  # noqa: E402
+
+DEV = "cuda:0"
+LR = 5e-4
+OURS = ("adam_sumsq_kernel", "adam_update_kernel")
+WAYS = ("torch", "fused", "hip", "torch_again")
+
+
+def parameter_sets():
+    """-> {name: [(shapes of group 0), (shapes of the lr * 10 group)]}."""
+    import bench  # noqa: F401
+    import test_generators as tg
+    import zest_networks
+    args = tg._args(precision=16, N_samples=128, pad=24, batch_size=1024, chunk=1024, num_extra_samples=0, use_motion_mask=False)
+    gen = tg._generator(args, train_builders=True)
+    disc = zest_networks.GRAFDiscriminator(3, 64, 64)
+    return {"generator": [[tuple(p.shape) for p in gen.parameters()], [(24, 8)]],          # time_codes: one row per frame
+            "discriminator_ndf64": [[tuple(p.shape) for p in disc.parameters()], []]}
+
+
+def build(way, clip, groups, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    params = [[torch.nn.Parameter((0.1 * torch.randn(s, generator=g)).to(DEV)) for s in shapes] for shapes in groups]
+    for ps in params:
+        for p in ps:
+            p.grad = (torch.randn(p.shape, generator=g) * 1e-2).to(DEV)
+    spec = [{"params": params[0]}] + ([{"params": params[1], "lr": LR * 10}] if params[1] else [])
+    flat = params[0] + params[1]
+    if way == "hip":
+        opt = zest_optim.Adam(spec, lr=LR, max_grad_norm=1.0 if clip else None)
+        return opt.step, opt
+    opt = torch.optim.Adam(spec, lr=LR, fused=True) if way == "fused" else torch.optim.Adam(spec, lr=LR)
+
+    def step():
+        if clip:
+            torch.nn.utils.clip_grad_norm_(flat, 1.0)
+        opt.step()
+    return step, opt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
+    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--loop", type=int, default=0, help="run only zest_optim.Adam with the clip this many times on each set")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_optimizer: no HIP device (there is no CPU path to time)")
+    sets = parameter_sets()
+    if a.loop:
+        for name, groups in sets.items():
+            step, _ = build("hip", True, groups, 0)
+            for _ in range(a.loop):
+                step()
+            torch.cuda.synchronize()
+        return
+    if a.iters < 200:
+        ap.error("--iters must be at least 200")
+    out = dict(bench="optimizer_step", iters=a.iters, block=a.block, warmup=a.warmup, lr=LR, device=torch.cuda.get_device_name(0), sets={})
+    for name, groups in sets.items():
+        shapes = groups[0] + groups[1]
+        elements = sum(int(torch.Size(s).numel()) for s in shapes)
+        res = dict(tensors=len(shapes), elements=elements)
+        for clip in (True, False):
+            steps = {w: build(w.split("_")[0], clip, groups, 0)[0] for w in WAYS}
+            for w in WAYS:
+                for _ in range(a.warmup):
+                    steps[w]()
+            torch.cuda.synchronize()
+            total = {w: 0.0 for w in WAYS}
+            done = 0
+            while done < a.iters:
+                n_it = min(a.block, a.iters - done)
+                for w in WAYS:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(n_it):
+                        steps[w]()
+                        torch.cuda.synchronize()
+                    total[w] += time.perf_counter() - t0
+                done += n_it
+            ms = {w: 1e3 * total[w] / a.iters for w in WAYS}
+            kernels = {}
+            for w in WAYS[:3]:
+                with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
+                    steps[w]()
+                    torch.cuda.synchronize()
+                evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+                       and not e.name.startswith(("Memcpy", "Memset", "Optimizer."))]    # the last: step's profiler range
+                kernels[w] = len(evs)
+                if w == "hip":
+                    kernels["hip_optim_hip"] = sum(any(k in e.name for k in OURS) for e in evs)
+                    kernels["hip_others"] = sorted(e.name[:80] for e in evs if not any(k in e.name for k in OURS))
+            spread = abs(ms["torch"] - ms["torch_again"])
+            gain = min(ms["torch"], ms["torch_again"]) - ms["hip"]
+            res["clip_1" if clip else "no_clip"] = dict(
+                ms_per_call={k: round(v, 4) for k, v in ms.items()}, kernels_per_call=kernels, torch_spread_ms=round(spread, 4),
+                gain_over_torch_ms=round(gain, 4), hip_faster_than_torch_by_more_than_spread=bool(gain > spread),
+                gain_over_fused_ms=round(ms["fused"] - ms["hip"], 4))
+        out["sets"][name] = res
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -25,7 +25,7 @@ import sys
 import types
 
 __all__ = ["install", "uninstall", "PATH_NAMES", "SF_LOSS_NAMES", "PATCH_LOSS_NAMES", "DISCRIMINATOR_NAMES",
-           "PERCEPTUAL_NAMES", "METRIC_NAMES", "main"]
+           "PERCEPTUAL_NAMES", "METRIC_NAMES", "OPTIMIZER_NAMES", "main"]
 
 # caller module -> (zest module, names rebound in the caller's module)
 PATH_NAMES = {
@@ -54,6 +54,9 @@ PERCEPTUAL_NAMES = ("LPIPS",)
 # opt-in (install(metrics=True) / ZEST_DROPIN_METRICS=1): `psnr` and `ssim` of the caller's own `kornia.metrics` become
 # zest_metrics.psnr / ssim (csrc/image_metrics.hip), before the caller's script does `from kornia.metrics import psnr, ssim`
 METRIC_NAMES = ("psnr", "ssim")
+# opt-in (install(optimizer=True) / ZEST_DROPIN_OPTIMIZER=1): `Adam` of the caller's own `torch.optim` becomes a factory that
+# returns a zest_optim.Adam (csrc/optim.hip) for fp32 parameters on a HIP device and options it builds, else the package's own
+OPTIMIZER_NAMES = ("Adam",)
 _saved = []          # (module, name, had, old) for uninstall()
 
 
@@ -91,8 +94,26 @@ def _lpips_factory(package_cls):
     return LPIPS
 
 
+def _adam_factory(package_cls):
+    """-> a callable with torch.optim.Adam's signature: a zest_optim.Adam where every parameter is fp32 on one HIP device
+    and the options are ones it builds (zest_optim.refusal), the package's own class otherwise - never an error the
+    package would not have raised.  It is a function: a caller that SUBCLASSES torch.optim.Adam must do so before."""
+    import zest_optim
+
+    def Adam(params, *args, **kwargs):
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            params = [dict(g, params=[g["params"]] if hasattr(g["params"], "dtype") else list(g["params"])) for g in params]
+        if zest_optim.refusal(params, *args, **kwargs) is None:
+            return zest_optim.Adam(params, *args, **kwargs)
+        return package_cls(params, *args, **kwargs)
+    Adam.__doc__ = "zest_dropin: torch.optim.Adam -> zest_optim.Adam where it is built, else the package's own"
+    Adam.__wrapped__ = package_cls
+    return Adam
+
+
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False, metrics=False):
+            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False, metrics=False, optimizer=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
@@ -104,6 +125,10 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
     by default: `lpips.LPIPS` stays the package's).
     metrics: also rebind `psnr` and `ssim` in the caller's `kornia.metrics` (imported here; ImportError if it is missing)
     to zest_metrics.psnr / ssim (off by default: they stay kornia's).
+    optimizer: also rebind `Adam` in the caller's `torch.optim` to a factory that returns a zest_optim.Adam for fp32
+    parameters on a HIP device and options it builds, and the package's own Adam otherwise (off by default: it stays
+    torch's).  A Trainer(gradient_clip_val=...) still clips on its own, in torch; the clip fused into the update is for
+    callers who pass max_grad_norm and drop gradient_clip_val.
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
     here = os.path.dirname(os.path.abspath(__file__))
@@ -150,6 +175,11 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
         for n in METRIC_NAMES:
             _bind(package, n, getattr(zest, n))
         done["kornia.metrics"] = sorted(METRIC_NAMES)
+    if optimizer:
+        package = importlib.import_module("torch.optim")
+        for n in OPTIMIZER_NAMES:
+            _bind(package, n, _adam_factory(getattr(package, n)))
+        done["torch.optim"] = sorted(OPTIMIZER_NAMES)
     return done
 
 
@@ -173,14 +203,15 @@ def main(argv=None):
               "regularisers of the static step (total_variation_loss, get_disparity_smoothness), ZEST_DROPIN_DISCRIMINATOR=1 "
               "the GRAF patch discriminator (networks.GRAFDiscriminator), ZEST_DROPIN_PERCEPTUAL=1 the LPIPS network "
               "(lpips.LPIPS, AlexNet backbone), ZEST_DROPIN_METRICS=1 the image metrics of the validation and test steps "
-              "(kornia.metrics.psnr, kornia.metrics.ssim)")
+              "(kornia.metrics.psnr, kornia.metrics.ssim), ZEST_DROPIN_OPTIMIZER=1 the optimiser (torch.optim.Adam)")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
     install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
             patch_losses=os.environ.get("ZEST_DROPIN_PATCH_LOSSES", "") == "1",
             discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1",
             perceptual=os.environ.get("ZEST_DROPIN_PERCEPTUAL", "") == "1",
-            metrics=os.environ.get("ZEST_DROPIN_METRICS", "") == "1")
+            metrics=os.environ.get("ZEST_DROPIN_METRICS", "") == "1",
+            optimizer=os.environ.get("ZEST_DROPIN_OPTIMIZER", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

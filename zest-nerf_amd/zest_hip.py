@@ -98,6 +98,13 @@ _SIGS = {
     "zest_image_metrics_work_bytes": (_sz, [_i, _i, _i, _i]),
     "zest_image_metrics": (_i, [_vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _i, _i, _i, _i, _i, _i, _f,
                                 _vp, _vp, _vp, _vp, _sz, _vp]),
+    "zest_adam_chunk": (_i, []),
+    "zest_adam_max_tensors": (_i, []),
+    "zest_adam_max_slots": (_i, []),
+    "zest_adam_plan": (C.c_longlong, [C.POINTER(C.c_longlong), _i, C.POINTER(_i), C.POINTER(C.c_longlong), C.c_longlong]),
+    "zest_adam_work_bytes": (_sz, [C.c_longlong]),
+    "zest_adam_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_vp), C.POINTER(_f), _i, _f,
+                            _vp, _sz, _vp, _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -812,6 +819,130 @@ def image_metrics(pred, target, window=5, clamp_pred=False, max_val=1.0, want_ma
                                 _ptr(result), _ptr(ssim_map), _ptr(abs_err), _ptr(work), need, _stream(pred)),
            "zest_image_metrics")
     return result, ssim_map, abs_err
+
+
+# ------------------------------------------------------------------------ optimiser (csrc/optim.hip)
+ADAM_TENSOR_COLS = 5              # device table row: addresses of p, exp_avg, exp_avg_sq; element count; row of scalars
+ADAM_SCALARS = 6                  # step_size, 1 / sqrt(bias_correction2), eps, 1 - b1, b2, 1 - b2
+
+
+def adam_chunk():
+    """-> elements of one chunk of csrc/optim.hip (no GPU call)."""
+    return lib().zest_adam_chunk()
+
+
+def adam_max_tensors():
+    """-> tensors whose gradient addresses one launch's argument block holds (no GPU call); more cost more launches."""
+    return lib().zest_adam_max_tensors()
+
+
+def adam_max_slots():
+    """-> rows of per-group, per-t scalars one launch's argument block holds (no GPU call)."""
+    return lib().zest_adam_max_slots()
+
+
+def adam_plan(sizes):
+    """The chunk plan of tensors of `sizes` elements (host only, no GPU call) -> ([tensor of chunk k], [offset of chunk
+    k in its tensor]); chunk k covers min(adam_chunk(), size - offset) elements."""
+    sizes = [int(n) for n in sizes]
+    L = lib()
+    arr = (C.c_longlong * max(len(sizes), 1))(*sizes)
+    n = L.zest_adam_plan(arr, len(sizes), None, None, 0)
+    if n < 0:
+        _check(1, "zest_adam_plan")
+    tens, offs = (_i * max(n, 1))(), (C.c_longlong * max(n, 1))()
+    if L.zest_adam_plan(arr, len(sizes), tens, offs, n) != n:
+        _check(1, "zest_adam_plan")
+    return list(tens[:n]), list(offs[:n])
+
+
+class AdamTable:
+    """What zest_adam_step reads that does not change from step to step: the device tables, the launch bounds, the
+    work buffer of the clip; built by adam_table()."""
+    __slots__ = ("device", "n_tensors", "n_chunks", "tensors", "chunk_tensor", "chunk_offset", "n_launches", "launch_tensor",
+                 "launch_chunk", "launch_keys", "work", "work_bytes", "scalars", "stamp")
+
+
+def adam_table(params, exp_avgs, exp_avg_sqs, keys):
+    """params, exp_avgs, exp_avg_sqs: equally long lists of non-empty contiguous fp32 tensors on one HIP device; keys:
+    per tensor a hashable that names its row of scalars (tensors of one parameter group at one step count share one).
+    -> AdamTable.  The step is cut into launches of at most adam_max_tensors() tensors and adam_max_slots() distinct keys;
+    .launch_keys[l] lists the keys of launch l in the order adam_step wants their scalars."""
+    who = "adam_table"
+    if not (len(params) == len(exp_avgs) == len(exp_avg_sqs) == len(keys)):
+        raise RuntimeError("zest_hip: %s: %d params, %d exp_avg, %d exp_avg_sq, %d keys" % (who, len(params), len(exp_avgs), len(exp_avg_sqs), len(keys)))
+    T = AdamTable()
+    T.n_tensors = len(params)
+    T.device = params[0].device if params else None
+    for name, ts in (("param", params), ("exp_avg", exp_avgs), ("exp_avg_sq", exp_avg_sqs)):
+        for i, (t, p) in enumerate(zip(ts, params)):
+            if not t.is_cuda:
+                raise RuntimeError("zest_hip: %s[%d] is on %s; this path runs only on a HIP device" % (name, i, t.device))
+            if t.device != T.device:
+                raise RuntimeError("zest_hip: %s: %s[%d] is on %s, param[0] on %s" % (who, name, i, t.device, T.device))
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.numel() == 0:
+                raise RuntimeError("zest_hip: %s: %s[%d] must be a non-empty contiguous fp32 tensor of %d elements, got %s %s"
+                                   % (who, name, i, p.numel(), t.dtype, tuple(t.shape)))
+    max_t, max_s = adam_max_tensors(), adam_max_slots()
+    chunk_tensor, chunk_offset = adam_plan([p.numel() for p in params])
+    T.n_chunks = len(chunk_tensor)
+    first_chunk = {}
+    for k, t in enumerate(chunk_tensor):
+        first_chunk.setdefault(t, k)
+    rows, bounds, T.launch_keys = [], [0], []
+    for i, (p, m, v, key) in enumerate(zip(params, exp_avgs, exp_avg_sqs, keys)):
+        if not T.launch_keys or i - bounds[-1] == max_t or (key not in T.launch_keys[-1] and len(T.launch_keys[-1]) == max_s):
+            if T.launch_keys:
+                bounds.append(i)
+            T.launch_keys.append([])
+        if key not in T.launch_keys[-1]:
+            T.launch_keys[-1].append(key)
+        rows.append([p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), T.launch_keys[-1].index(key)])
+    if T.n_tensors:
+        bounds.append(T.n_tensors)
+    T.n_launches = len(T.launch_keys)
+    T.launch_tensor = (_i * (T.n_launches + 1))(*bounds)
+    T.launch_chunk = (C.c_longlong * (T.n_launches + 1))(*[first_chunk[b] if b < T.n_tensors else T.n_chunks for b in bounds])
+    T.scalars = (_f * (max(T.n_launches, 1) * max_s * ADAM_SCALARS))()
+    T.work_bytes = lib().zest_adam_work_bytes(T.n_chunks)
+    if T.n_tensors:
+        dev = T.device
+        T.tensors = torch.tensor(rows, dtype=torch.int64).to(dev)
+        T.chunk_tensor = torch.tensor(chunk_tensor, dtype=torch.int32).to(dev)
+        T.chunk_offset = torch.tensor(chunk_offset, dtype=torch.int64).to(dev)
+        T.work = torch.empty(T.work_bytes, device=dev, dtype=torch.uint8)
+    else:
+        T.tensors = T.chunk_tensor = T.chunk_offset = T.work = None
+    return T
+
+
+def adam_step(table, grads, scalars, max_norm=None):
+    """One Adam step of the tensors of `table` in table.n_launches launches, twice as many with the clip.
+    grads: one contiguous fp32 tensor per tensor of the table, of its size, on its device (their addresses travel in the
+    launches' argument blocks; they are only read).  scalars: {key: the ADAM_SCALARS floats of that key} for every key of
+    table.launch_keys.  max_norm: None, or the global 2-norm the gradients are clipped to while they are applied
+    -> None (also for a table without tensors), or the 0-d device tensor of the unclipped norm."""
+    who = "adam_step"
+    if len(grads) != table.n_tensors:
+        raise RuntimeError("zest_hip: %s: %d gradients for a table of %d tensors" % (who, len(grads), table.n_tensors))
+    for i, g in enumerate(grads):
+        if not g.is_cuda:
+            raise RuntimeError("zest_hip: grads[%d] is on %s; this path runs only on a HIP device" % (i, g.device))
+    if table.n_tensors == 0:
+        return None
+    ptrs = (_vp * table.n_tensors)(*[g.data_ptr() for g in grads])
+    sc, row = table.scalars, adam_max_slots() * ADAM_SCALARS
+    for l, keys in enumerate(table.launch_keys):
+        for k, key in enumerate(keys):
+            o = l * row + k * ADAM_SCALARS
+            sc[o:o + ADAM_SCALARS] = scalars[key]
+    dev = table.device
+    norm = None if max_norm is None else torch.empty((), device=dev, dtype=torch.float32)
+    _check(lib().zest_adam_step(_ptr(table.tensors), _ptr(table.chunk_tensor), _ptr(table.chunk_offset), table.n_launches,
+                                table.launch_tensor, table.launch_chunk, ptrs, sc, int(max_norm is not None),
+                                0.0 if max_norm is None else float(max_norm), _ptr(table.work), table.work_bytes, _ptr(norm),
+                                torch.cuda.current_stream(dev).cuda_stream), "zest_adam_step")
+    return norm
 
 
 def nchw_to_nhwc(x):

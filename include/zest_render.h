@@ -213,6 +213,19 @@ int zest_costreg_bn_bwd(const float *raw, const float *g_act, const float *pre, 
                         void *stream);
 int zest_costreg_out(const float *raw_a, const float *pre_a, const float *raw_b, const float *pre_b, int D,
                      int H, int W, float *volume, void *stream);
+/* Weight gradient of the net's first layer (Conv3d 3 x 3 x 3, stride 1, padding 1, cin <= 48 -> 8 channels) from the
+ * channels-last tensors of the training step: x [D,H,W,48] (the padded cost volume the forward reads; channels from
+ * cin on are never read into a product), g [D,H,W,8] (g_raw of zest_costreg_bn_bwd), any D, H, W >= 1.
+ *   g_w[co][ci][kz][ky][kx] = sum_v g[v][co] x[v + (kz-1, ky-1, kx-1)][ci]   (x = 0 outside the volume)
+ * Operands rounded to bf16 (nearest even), fp32 accumulation, g_w [8,cin,3,3,3] fp32.  Two launches: every workgroup
+ * writes a partial [27][8][48] to `work` (zest_costreg_wgrad_work_bytes(D, H, W) bytes, 16-byte aligned), a finishing
+ * kernel adds them in a fixed order - no atomics, the same bits on every call.
+ * zest_costreg_wgrad_launch_shape: host arithmetic only.  A unit is 4 rows of one slice (D ceil(H / 4) units);
+ *   workgroup w of *n_wg (at most 768) takes units [w *units_per_wg, (w + 1) *units_per_wg); result pointers may be NULL. */
+int zest_costreg_wgrad_launch_shape(int D, int H, int W, int *units_per_wg, int *n_wg);
+size_t zest_costreg_wgrad_work_bytes(int D, int H, int W);
+int zest_costreg_wgrad(const float *x, const float *g, int D, int H, int W, int cin, int cout, void *work,
+                       float *g_w, void *stream);
 
 /* Backward of the plane sweep (the MVSNet trains through it: reference train.py:270 optimises
  * generator.parameters(), networks.py:1077-1140 runs under autograd).  The trainable input is the

@@ -526,20 +526,33 @@ class CostRegFn(Function):
     8-11 ms): the raw output of every layer, its norm constants and batch moments are kept, and the backward pass
     walks the U-Net in reverse with the library's own backward operators on them (aten.convolution_backward,
     aten.native_batch_norm_backward; the leaky ReLU and the skip additions are a few elementwise operations).
-    Inputs after `passes`: the ten convolution weights, then (weight, bias) of the ten norms, in layer order."""
+    hip_wgrad (MVSNet.zest_hip_costreg_wgrad; bf16 operands, passes == 1, only - with passes == 3 it changes nothing):
+    the weight gradient of layer 0, the one layer that reads the 41-channel cost volume at full resolution, comes from
+    zest_costreg_wgrad (csrc/costreg_wgrad.hip: fp32 result, not rounded to bf16) and the library is asked for that
+    layer's data gradient only, which needs neither the bf16 copy of the cost volume nor its values.  The price: the
+    padded channels-last copy of the cost volume [D,H,W,48] fp32 that the forward builds is kept until the backward
+    pass, 0.5 GB per volume builder at 128 x 120 x 176.
+    Inputs after `hip_wgrad`: the ten convolution weights, then (weight, bias) of the ten norms, in layer order."""
 
     @staticmethod
-    def forward(ctx, cost, net, passes, *params):
+    def forward(ctx, cost, net, passes, hip_wgrad, *params):
         cl = torch.nn.functional.pad(cost[0].permute(1, 2, 3, 0), (0, zest_hip.COST_CL_CHANNELS - cost.shape[1])).contiguous()
         vol, raw, pr, mo = net.forward_hip(cl, passes, keep=True)
         ctx.net, ctx.passes, ctx.n = net, passes, len(raw)
-        ctx.save_for_backward(cost, *raw, *pr, *mo, *params)
+        ctx.hip_wgrad = bool(hip_wgrad) and passes == 1
+        if ctx.hip_wgrad:
+            ctx.save_for_backward(cost, *raw, *pr, *mo, *params, cl)
+        else:
+            ctx.save_for_backward(cost, *raw, *pr, *mo, *params)
         return vol
 
     @staticmethod
     def backward(ctx, g_out):
         t = ctx.saved_tensors
         n = ctx.n
+        cl = None
+        if ctx.hip_wgrad:
+            t, cl = t[:-1], t[-1]
         cost, raw, pr, mo, params = t[0], t[1:1 + n], t[1 + n:1 + 2 * n], t[1 + 2 * n:1 + 3 * n], t[1 + 3 * n:]
         W, gam = params[:n], params[n::2]
         net = ctx.net
@@ -565,6 +578,17 @@ class CostRegFn(Function):
             g_x, g_w, _ = torch.ops.aten.convolution_backward(g_r, x, w, None, [stride] * 3, [1] * 3, [1] * 3, transposed,
                                                               [1 if transposed else 0] * 3, 1, [want_x, True, False])
             return (g_x.float() if want_x else None), g_w.float()
+
+        def conv0_bwd(g_r, want_x):
+            """Layer 0 with hip_wgrad: the weight gradient from zest_costreg_wgrad on the kept channels-last tensors
+            (g_r is a view of costreg_bn_bwd's [D,H,W,8] result), the data gradient alone from the library - which
+            reads no input value for it, so an uninitialised bf16 tensor of the cost volume's sizes stands in."""
+            g_w = zest_hip.costreg_wgrad(cl, g_r[0].permute(1, 2, 3, 0), cost.shape[1])
+            if not want_x:
+                return None, g_w
+            g_x, _, _ = torch.ops.aten.convolution_backward(g_r.to(low), torch.empty_like(cost, dtype=low), W[0].to(low), None,
+                                                            [1] * 3, [1] * 3, [1] * 3, False, [0] * 3, 1, [True, False, False])
+            return g_x.float(), g_w
         gW, gG, gB = [None] * n, [None] * n, [None] * n
         g_out = g_out.contiguous()
         # up path (layers 9, 8, 7 = conv11, conv9, conv7), skip additions on the way
@@ -581,22 +605,25 @@ class CostRegFn(Function):
             if i in skip:
                 g_a = g_a + skip[i]
             g_r, gG[i], gB[i] = norm_bwd(i, g_a)
+            if i == 0 and cl is not None:
+                g_a, gW[0] = conv0_bwd(g_r, ctx.needs_input_grad[0])
+                break
             x = act(i - 1) if i > 0 else cost
             g_a, gW[i] = conv_bwd(g_r, x, W[i], strides[i], False, want_x=(i > 0 or ctx.needs_input_grad[0]))
         grads = list(gW)
         for i in range(n):
             grads += [gG[i], gB[i]]
-        return (g_a, None, None) + tuple(grads)
+        return (g_a, None, None, None) + tuple(grads)
 
 
-def costreg_apply(net, cost_vol, passes):
-    """CostRegNet(cost_vol [1,41,D,H,W]) -> [1,8,D,H,W] through CostRegFn."""
+def costreg_apply(net, cost_vol, passes, hip_wgrad=False):
+    """CostRegNet(cost_vol [1,41,D,H,W]) -> [1,8,D,H,W] through CostRegFn.  hip_wgrad: see there (opt-in; passes == 1 only)."""
     convs = [getattr(net, nm).conv for nm, _ in net._HIP_CONVS] + [getattr(net, nm)[0] for nm in net._HIP_UPS]
     bns = [getattr(net, nm).bn for nm, _ in net._HIP_CONVS] + [getattr(net, nm)[1] for nm in net._HIP_UPS]
     params = [c.weight for c in convs]
     for b in bns:
         params += [b.weight, b.bias]
-    return CostRegFn.apply(cost_vol.float(), net, passes, *params)
+    return CostRegFn.apply(cost_vol.float(), net, passes, bool(hip_wgrad), *params)
 
 
 class FeatureFn(Function):

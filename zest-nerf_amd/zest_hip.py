@@ -120,6 +120,9 @@ _SIGS = {
     "zest_costreg_bn": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _f, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "zest_costreg_out": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "zest_costreg_bn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "zest_costreg_wgrad_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "zest_costreg_wgrad_work_bytes": (_sz, [_i, _i, _i]),
+    "zest_costreg_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_lookup_fwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
@@ -1117,6 +1120,60 @@ def costreg_bn_bwd(raw, g_act, pre, moments, gamma):
     _check(lib().zest_costreg_bn_bwd(_ptr(raw), _ptr(g_act), _ptr(pre), _ptr(moments), _ptr(gamma), Cn, M, _ptr(stats),
                                      _ptr(totals), _ptr(g_raw), _stream(raw)), "zest_costreg_bn_bwd")
     return g_raw, totals[1], totals[0]
+
+
+def costreg_wgrad_launch_shape(D, H, W):
+    """-> (units per workgroup, workgroups) of the first layer's weight-gradient kernel on a D x H x W volume (a unit:
+    four rows of one slice; workgroup w takes units [w upw, (w + 1) upw)).  Host arithmetic, the same code the launch runs."""
+    upw, wgs = _i(0), _i(0)
+    _check(lib().zest_costreg_wgrad_launch_shape(int(D), int(H), int(W), C.byref(upw), C.byref(wgs)),
+           "zest_costreg_wgrad_launch_shape")
+    return upw.value, wgs.value
+
+
+def costreg_wgrad_work_floats(D, H, W):
+    """Size of the partial-sum buffer of costreg_wgrad, in fp32 elements."""
+    n = int(lib().zest_costreg_wgrad_work_bytes(int(D), int(H), int(W)))
+    if n == 0:
+        _check(1, "zest_costreg_wgrad_work_bytes")
+    return n // 4
+
+
+def costreg_wgrad(x_cl, g_cl, cin, work=None, out=None):
+    """Weight gradient of CostRegNet.conv0: x_cl [D,H,W,48] (the padded channels-last cost volume of the forward; channels
+    from `cin` on are not read into the result), g_cl [D,H,W,8] (costreg_bn_bwd's g_raw) -> g_w [8,cin,3,3,3] fp32.
+    bf16-rounded operands, fp32 accumulation, no atomics.  work / out: the caller's buffers (costreg_wgrad_work_floats
+    fp32 elements, 16-byte aligned; [8,cin,3,3,3]) instead of fresh ones."""
+    who = "zest_hip.costreg_wgrad"
+    # dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device
+    for nm, t, ch in (("x_cl", x_cl, COST_CL_CHANNELS), ("g_cl", g_cl, 8)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or t.shape[3] != ch:
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor [D,H,W,%d], got %s"
+                               % (who, nm, ch, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
+                                  if torch.is_tensor(t) else type(t).__name__))
+    D, H, W, _ = x_cl.shape
+    if tuple(g_cl.shape[:3]) != (D, H, W):
+        raise RuntimeError("%s: g_cl %s against x_cl %s" % (who, tuple(g_cl.shape), tuple(x_cl.shape)))
+    cin = int(cin)
+    if not 1 <= cin <= COST_CL_CHANNELS:
+        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
+    for nm, t in (("x_cl", x_cl), ("g_cl", g_cl)):
+        if not t.is_cuda or t.device != x_cl.device:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
+    need = costreg_wgrad_work_floats(D, H, W)
+    if work is None:
+        work = torch.empty(need, device=x_cl.device, dtype=torch.float32)
+    elif (work.device != x_cl.device or work.dtype != torch.float32 or not work.is_contiguous() or work.numel() != need
+          or work.data_ptr() % 16):
+        raise RuntimeError("%s: work must be %d contiguous fp32 elements on %s, 16-byte aligned" % (who, need, x_cl.device))
+    if out is None:
+        out = torch.empty(8, cin, 3, 3, 3, device=x_cl.device, dtype=torch.float32)
+    elif (out.device != x_cl.device or out.dtype != torch.float32 or not out.is_contiguous()
+          or tuple(out.shape) != (8, cin, 3, 3, 3)):
+        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, (8, cin, 3, 3, 3), x_cl.device))
+    _check(lib().zest_costreg_wgrad(_ptr(x_cl), _ptr(g_cl), D, H, W, cin, 8, _ptr(work), _ptr(out), _stream(x_cl)),
+           "zest_costreg_wgrad")
+    return out
 
 
 def costreg_out(raw_a, pre_a, raw_b, pre_b):

@@ -626,6 +626,10 @@ class MVSNet(nn.Module):
         self.feature = FeatureNet()
         self.chunk = 1024
         self.cost_reg_2 = CostRegNet(32 + 9, norm_act)
+        # opt-in: under autograd in bf16 (--precision 16) the weight gradient of cost_reg_2.conv0 from the HIP kernel
+        # (zest_autograd.CostRegFn; keeps a [D,H,W,48] fp32 copy of the cost volume, 0.5 GB at 128 x 120 x 176, until
+        # the backward pass).  No effect in fp32 mode.
+        self.zest_hip_costreg_wgrad = False
 
     def build_volume_cost(self, imgs, feats, proj_mats, depth_values, pad=0):
         """imgs [1,V,3,Hi,Wi]; feats [1,V,32,H,W]; proj_mats [1,V,3,4]; depth_values [1,D]
@@ -708,7 +712,9 @@ class MVSNet(nn.Module):
                 and all(m.training for m in self.cost_reg_2.modules() if isinstance(m, ActivatedBatchNorm))):
             # backward: HIP norm kernels + the library's convolution backward on the kept raw outputs
             import zest_autograd
-            volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes)
+            # zest_hip_costreg_wgrad (opt-in, --precision 16 only): the first layer's weight gradient in HIP as well
+            volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes,
+                                                      hip_wgrad=bool(getattr(self, "zest_hip_costreg_wgrad", False)))
         else:
             volume_feat, _ = self.cost_reg_2(cost_vol)
         volume_feat = volume_feat.reshape(1, -1, *volume_feat.shape[2:])
@@ -750,6 +756,8 @@ class _Generator(nn.Module):
                 return self._volume_replayed(net, imgs, proj_mats, near_far)
             if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_train", None) is not None:
                 net.zest_hip_costreg_train = bool(self.args.zest_hip_costreg_train)       # the caller's choice, else MVSNet's default
+            if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_wgrad", None) is not None:
+                net.zest_hip_costreg_wgrad = bool(self.args.zest_hip_costreg_wgrad)
             return net(imgs, proj_mats, near_far, pad=self.args.pad)[0].float()
 
     def _volume_replayed(self, net, imgs, proj_mats, near_far):

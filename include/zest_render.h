@@ -226,6 +226,19 @@ int zest_costreg_wgrad_launch_shape(int D, int H, int W, int *units_per_wg, int 
 size_t zest_costreg_wgrad_work_bytes(int D, int H, int W);
 int zest_costreg_wgrad(const float *x, const float *g, int D, int H, int W, int cin, int cout, void *work,
                        float *g_w, void *stream);
+/* Data gradient of the same layer, from g [D,H,W,8] (as above) and the module's weight w [8,cin,3,3,3] fp32, cin <= 48:
+ *   g_x[ci][z][y][x] = sum_{co,kz,ky,kx} g[z+1-kz][y+1-ky][x+1-kx][co] w[co][ci][kz][ky][kx]   (g = 0 outside the volume)
+ * Operands rounded to bf16 (nearest even; the weight is mirrored and packed on the device, in the kernel), fp32
+ * accumulation, g_x [cin,D,H,W] fp32 channel planes - what zest_volume_cost_bwd reads.  One launch, a gather: every
+ * element of g_x is written exactly once, no atomics, no zeroing beforehand, the same bits on every call.  g, w and g_x
+ * 16-byte aligned; D H W 48 < 2^31.
+ * zest_costreg_dgrad_launch_shape: host arithmetic only.  A tile is 32 voxels in x by 2 rows of one slice
+ *   (*n_tiles = D ceil(H / 2) ceil(W / 32), numbered with x fastest, then y, then z); workgroup w of *n_wg (at most 1024)
+ *   takes tiles [w tpw, (w + 1) tpw), tpw = ceil(*n_tiles / 1024), its four waves every fourth one; result pointers may
+ *   be NULL. */
+int zest_costreg_dgrad_launch_shape(int D, int H, int W, int *n_tiles, int *n_wg);
+int zest_costreg_dgrad(const float *g, const float *w, int D, int H, int W, int cin, int cout, float *g_x,
+                       void *stream);
 
 /* Backward of the plane sweep (the MVSNet trains through it: reference train.py:270 optimises
  * generator.parameters(), networks.py:1077-1140 runs under autograd).  The trainable input is the

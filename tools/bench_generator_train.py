@@ -13,6 +13,7 @@ ap.add_argument("--precision", type=int, default=16)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--library-costreg", action="store_true", help="MVSNet.zest_hip_costreg_train = False: the regularisation nets through the library under autograd (the product default in --precision 16 is their forward on the HIP kernels, zest_autograd.CostRegFn)")
 ap.add_argument("--hip-wgrad", action="store_true", help="MVSNet.zest_hip_costreg_wgrad = True: the weight gradient of each regularisation net's first layer from zest_costreg_wgrad (csrc/costreg_wgrad.hip) instead of the library (--precision 16 only)")
+ap.add_argument("--hip-dgrad", action="store_true", help="MVSNet.zest_hip_costreg_dgrad = True: the data gradient of each regularisation net's first layer from zest_costreg_dgrad (csrc/costreg_dgrad.hip) instead of the library (--precision 16 only)")
 a = ap.parse_args()
 torch.backends.cudnn.benchmark = True
 x = tg._batch(7, H=288, W=512)
@@ -22,6 +23,8 @@ if a.library_costreg:
     args.zest_hip_costreg_train = False
 if a.hip_wgrad:
     args.zest_hip_costreg_wgrad = True
+if a.hip_dgrad:
+    args.zest_hip_costreg_dgrad = True
 
 
 def step():

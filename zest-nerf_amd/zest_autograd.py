@@ -532,6 +532,11 @@ class CostRegFn(Function):
     layer's data gradient only, which needs neither the bf16 copy of the cost volume nor its values.  The price: the
     padded channels-last copy of the cost volume [D,H,W,48] fp32 that the forward builds is kept until the backward
     pass, 0.5 GB per volume builder at 128 x 120 x 176.
+    net.zest_hip_dgrad (MVSNet.zest_hip_costreg_dgrad; read in forward, passes == 1 only as well): the data gradient of
+    layer 0 - the gradient towards the cost volume - comes from zest_costreg_dgrad (csrc/costreg_dgrad.hip) on
+    zest_costreg_bn_bwd's channels-last result and the module's fp32 weight: fp32 channel planes, no casts, no
+    transposes, nothing extra kept.  The library is then asked only for what is still missing: the weight gradient
+    without hip_wgrad, nothing with it (no bf16 stand-in for the cost volume either).
     Inputs after `hip_wgrad`: the ten convolution weights, then (weight, bias) of the ten norms, in layer order."""
 
     @staticmethod
@@ -540,6 +545,7 @@ class CostRegFn(Function):
         vol, raw, pr, mo = net.forward_hip(cl, passes, keep=True)
         ctx.net, ctx.passes, ctx.n = net, passes, len(raw)
         ctx.hip_wgrad = bool(hip_wgrad) and passes == 1
+        ctx.hip_dgrad = bool(getattr(net, "zest_hip_dgrad", False)) and passes == 1
         if ctx.hip_wgrad:
             ctx.save_for_backward(cost, *raw, *pr, *mo, *params, cl)
         else:
@@ -580,15 +586,23 @@ class CostRegFn(Function):
             return (g_x.float() if want_x else None), g_w.float()
 
         def conv0_bwd(g_r, want_x):
-            """Layer 0 with hip_wgrad: the weight gradient from zest_costreg_wgrad on the kept channels-last tensors
-            (g_r is a view of costreg_bn_bwd's [D,H,W,8] result), the data gradient alone from the library - which
-            reads no input value for it, so an uninitialised bf16 tensor of the cost volume's sizes stands in."""
-            g_w = zest_hip.costreg_wgrad(cl, g_r[0].permute(1, 2, 3, 0), cost.shape[1])
-            if not want_x:
-                return None, g_w
-            g_x, _, _ = torch.ops.aten.convolution_backward(g_r.to(low), torch.empty_like(cost, dtype=low), W[0].to(low), None,
-                                                            [1] * 3, [1] * 3, [1] * 3, False, [0] * 3, 1, [True, False, False])
-            return g_x.float(), g_w
+            """Layer 0 with hip_wgrad and / or hip_dgrad, on the channels-last tensors (g_r is a view of costreg_bn_bwd's
+            [D,H,W,8] result): the weight gradient from zest_costreg_wgrad on the kept cost volume, the data gradient
+            from zest_costreg_dgrad on the fp32 weight; the library gives the one that is not taken from a kernel - for
+            the data gradient alone it reads no input value, so an uninitialised bf16 tensor of the cost volume's
+            sizes stands in."""
+            g_cl0 = g_r[0].permute(1, 2, 3, 0)
+            g_x = zest_hip.costreg_dgrad(g_cl0, W[0])[None] if (want_x and ctx.hip_dgrad) else None
+            if cl is None:
+                _, g_w, _ = torch.ops.aten.convolution_backward(g_r.to(low), cost.to(low), W[0].to(low), None, [1] * 3, [1] * 3,
+                                                                [1] * 3, False, [0] * 3, 1, [False, True, False])
+                return g_x, g_w.float()
+            g_w = zest_hip.costreg_wgrad(cl, g_cl0, cost.shape[1])
+            if want_x and g_x is None:
+                g_x, _, _ = torch.ops.aten.convolution_backward(g_r.to(low), torch.empty_like(cost, dtype=low), W[0].to(low), None,
+                                                                [1] * 3, [1] * 3, [1] * 3, False, [0] * 3, 1, [True, False, False])
+                g_x = g_x.float()
+            return g_x, g_w
         gW, gG, gB = [None] * n, [None] * n, [None] * n
         g_out = g_out.contiguous()
         # up path (layers 9, 8, 7 = conv11, conv9, conv7), skip additions on the way
@@ -605,7 +619,7 @@ class CostRegFn(Function):
             if i in skip:
                 g_a = g_a + skip[i]
             g_r, gG[i], gB[i] = norm_bwd(i, g_a)
-            if i == 0 and cl is not None:
+            if i == 0 and (cl is not None or (ctx.hip_dgrad and ctx.needs_input_grad[0])):
                 g_a, gW[0] = conv0_bwd(g_r, ctx.needs_input_grad[0])
                 break
             x = act(i - 1) if i > 0 else cost

@@ -123,6 +123,8 @@ _SIGS = {
     "zest_costreg_wgrad_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "zest_costreg_wgrad_work_bytes": (_sz, [_i, _i, _i]),
     "zest_costreg_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "zest_costreg_dgrad_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "zest_costreg_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "zest_volume_cost_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_lookup_fwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
@@ -1173,6 +1175,45 @@ def costreg_wgrad(x_cl, g_cl, cin, work=None, out=None):
         raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, (8, cin, 3, 3, 3), x_cl.device))
     _check(lib().zest_costreg_wgrad(_ptr(x_cl), _ptr(g_cl), D, H, W, cin, 8, _ptr(work), _ptr(out), _stream(x_cl)),
            "zest_costreg_wgrad")
+    return out
+
+
+def costreg_dgrad_launch_shape(D, H, W):
+    """-> (tiles, workgroups) of the first layer's data-gradient kernel on a D x H x W volume (a tile: 32 voxels in x by
+    two rows of one slice; workgroup w takes tiles [w tpw, (w + 1) tpw), tpw = ceil(tiles / 1024)).  Host arithmetic,
+    the same code the launch runs."""
+    n_tiles, wgs = _i(0), _i(0)
+    _check(lib().zest_costreg_dgrad_launch_shape(int(D), int(H), int(W), C.byref(n_tiles), C.byref(wgs)),
+           "zest_costreg_dgrad_launch_shape")
+    return n_tiles.value, wgs.value
+
+
+def costreg_dgrad(g_cl, weight, out=None):
+    """Data gradient of CostRegNet.conv0: g_cl [D,H,W,8] (costreg_bn_bwd's g_raw), weight [8,cin,3,3,3] (the module's
+    own, cin 1 .. 48) -> g_x [cin,D,H,W] fp32 channel planes.  bf16-rounded operands, fp32 accumulation, every element
+    written once, no atomics.  out: the caller's [cin,D,H,W] buffer instead of a fresh one."""
+    who = "zest_hip.costreg_dgrad"
+    # dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device
+    for nm, t, what, ok in (("g_cl", g_cl, "[D,H,W,8]", lambda t: t.dim() == 4 and t.shape[3] == 8),
+                            ("weight", weight, "[8,cin,3,3,3]", lambda t: t.dim() == 5 and t.shape[0] == 8 and tuple(t.shape[2:]) == (3, 3, 3))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
+                               % (who, nm, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
+                                  if torch.is_tensor(t) else type(t).__name__))
+    D, H, W, _ = g_cl.shape
+    cin = int(weight.shape[1])
+    if not 1 <= cin <= COST_CL_CHANNELS:
+        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
+    for nm, t in (("g_cl", g_cl), ("weight", weight)):
+        if not t.is_cuda or t.device != g_cl.device:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
+    if out is None:
+        out = torch.empty(cin, D, H, W, device=g_cl.device, dtype=torch.float32)
+    elif (not torch.is_tensor(out) or out.device != g_cl.device or out.dtype != torch.float32 or not out.is_contiguous()
+          or tuple(out.shape) != (cin, D, H, W)):
+        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, (cin, D, H, W), g_cl.device))
+    _check(lib().zest_costreg_dgrad(_ptr(g_cl), _ptr(weight), D, H, W, cin, 8, _ptr(out), _stream(g_cl)),
+           "zest_costreg_dgrad")
     return out
 
 

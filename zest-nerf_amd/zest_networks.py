@@ -502,6 +502,9 @@ class CostRegNet(nn.Module):
         up = lambda i, o: nn.Sequential(
             nn.ConvTranspose3d(i, o, 3, padding=1, output_padding=1, stride=2, bias=False), norm_act(o))
         self.conv7, self.conv9, self.conv11 = up(64, 32), up(32, 16), up(16, 8)
+        # opt-in, set by MVSNet.forward from its zest_hip_costreg_dgrad: zest_autograd.CostRegFn takes conv0's data
+        # gradient from the HIP kernel (csrc/costreg_dgrad.hip; bf16 operands, passes == 1, only)
+        self.zest_hip_dgrad = False
 
     # ---- HIP path, no autograd (csrc/costreg.hip): channels-last tensors, a layer's norm + activation applied by
     # the layer that reads it, batch statistics from the convolution kernels themselves
@@ -630,6 +633,9 @@ class MVSNet(nn.Module):
         # (zest_autograd.CostRegFn; keeps a [D,H,W,48] fp32 copy of the cost volume, 0.5 GB at 128 x 120 x 176, until
         # the backward pass).  No effect in fp32 mode.
         self.zest_hip_costreg_wgrad = False
+        # opt-in, likewise: the data gradient of cost_reg_2.conv0 - the gradient towards the cost volume - from the HIP
+        # kernel, as fp32 channel planes (nothing extra is kept for it).  No effect in fp32 mode.
+        self.zest_hip_costreg_dgrad = False
 
     def build_volume_cost(self, imgs, feats, proj_mats, depth_values, pad=0):
         """imgs [1,V,3,Hi,Wi]; feats [1,V,32,H,W]; proj_mats [1,V,3,4]; depth_values [1,D]
@@ -712,7 +718,9 @@ class MVSNet(nn.Module):
                 and all(m.training for m in self.cost_reg_2.modules() if isinstance(m, ActivatedBatchNorm))):
             # backward: HIP norm kernels + the library's convolution backward on the kept raw outputs
             import zest_autograd
-            # zest_hip_costreg_wgrad (opt-in, --precision 16 only): the first layer's weight gradient in HIP as well
+            # zest_hip_costreg_wgrad (opt-in, --precision 16 only): the first layer's weight gradient in HIP as well;
+            # zest_hip_costreg_dgrad (likewise): its data gradient - the switch travels on the module
+            self.cost_reg_2.zest_hip_dgrad = bool(getattr(self, "zest_hip_costreg_dgrad", False))
             volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes,
                                                       hip_wgrad=bool(getattr(self, "zest_hip_costreg_wgrad", False)))
         else:
@@ -758,6 +766,8 @@ class _Generator(nn.Module):
                 net.zest_hip_costreg_train = bool(self.args.zest_hip_costreg_train)       # the caller's choice, else MVSNet's default
             if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_wgrad", None) is not None:
                 net.zest_hip_costreg_wgrad = bool(self.args.zest_hip_costreg_wgrad)
+            if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_dgrad", None) is not None:
+                net.zest_hip_costreg_dgrad = bool(self.args.zest_hip_costreg_dgrad)
             return net(imgs, proj_mats, near_far, pad=self.args.pad)[0].float()
 
     def _volume_replayed(self, net, imgs, proj_mats, near_far):

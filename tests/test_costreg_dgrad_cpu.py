@@ -155,7 +155,9 @@ def test_switch_reaches_the_net_through_the_builder_and_the_generator():
 
     net = Net()
     assert net.zest_hip_costreg_dgrad is False and networks.MVSNet().zest_hip_costreg_dgrad is False
-    assert networks.CostRegNet(41).zest_hip_dgrad is False and net.cost_reg_2.zest_hip_dgrad is False
+    # the switch is an argument of costreg_apply, not a field of the regularisation net (the way from MVSNet.forward to
+    # costreg_apply needs a device: tests/test_hip_costreg_dgrad.py)
+    assert not hasattr(networks.CostRegNet(41), "zest_hip_dgrad") and not hasattr(net.cost_reg_2, "zest_hip_dgrad")
     gen = networks._Generator()
     imgs = torch.zeros(1, 3, 3, 8, 8)
     for given, want in (((), False), ((None,), False), ((True,), True), ((None,), True), ((0,), False), ((1,), True)):
@@ -173,5 +175,7 @@ def test_costreg_apply_keeps_its_signature():
     import inspect
     import zest_autograd
     sig = inspect.signature(zest_autograd.costreg_apply)
-    assert list(sig.parameters) == ["net", "cost_vol", "passes", "hip_wgrad"] and sig.parameters["hip_wgrad"].default is False
-    assert "zest_hip_dgrad" in zest_autograd.CostRegFn.__doc__
+    assert list(sig.parameters) == ["net", "cost_vol", "passes", "hip_wgrad", "hip_dgrad"]
+    assert sig.parameters["hip_wgrad"].default is False and sig.parameters["hip_dgrad"].default is False
+    assert list(inspect.signature(zest_autograd.CostRegFn.forward).parameters)[:6] == ["ctx", "cost", "net", "passes", "hip_wgrad", "hip_dgrad"]
+    assert "hip_dgrad (MVSNet.zest_hip_costreg_dgrad)" in zest_autograd.CostRegFn.__doc__

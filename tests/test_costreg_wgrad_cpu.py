@@ -164,5 +164,6 @@ def test_costreg_apply_takes_the_switch_and_defaults_to_off():
     import inspect
     import zest_autograd
     sig = inspect.signature(zest_autograd.costreg_apply)
-    assert list(sig.parameters) == ["net", "cost_vol", "passes", "hip_wgrad"] and sig.parameters["hip_wgrad"].default is False
+    assert list(sig.parameters) == ["net", "cost_vol", "passes", "hip_wgrad", "hip_dgrad"]
+    assert sig.parameters["hip_wgrad"].default is False and sig.parameters["hip_dgrad"].default is False
     assert "0.5 GB" in zest_autograd.CostRegFn.__doc__

@@ -89,7 +89,7 @@ def test_two_calls_give_the_same_bits(hip):
 
 def test_through_the_regularisation_net(hip):
     """CostRegFn on a (16, 16, 24) volume with bf16 operands (passes = 1), training-mode norms, the same seed: one run
-    with net.zest_hip_dgrad on, two with it off.  The cost gradient: (1, 41, 16, 16, 24) fp32, relative L2 difference
+    with hip_dgrad on, two with it off.  The cost gradient: (1, 41, 16, 16, 24) fp32, relative L2 difference
     below 1e-2 (the library rounds its result to bf16, 2^-9 per element).  Every parameter gradient: at most 1e-6
     relative L2 plus four times what the two off runs differ by.  The saved tensors are the same in number.  With the
     weight-gradient kernel on as well the cost gradient is the same, bit for bit.  passes = 3 ignores the switch."""
@@ -106,12 +106,8 @@ def test_through_the_regularisation_net(hip):
 
     def run(dgrad, passes=1, wgrad=False):
         net.zero_grad(set_to_none=True)
-        net.zest_hip_dgrad = dgrad
-        try:
-            c = cost.clone().requires_grad_(True)
-            out = zest_autograd.costreg_apply(net, c, passes, hip_wgrad=wgrad)
-        finally:
-            net.zest_hip_dgrad = False
+        c = cost.clone().requires_grad_(True)
+        out = zest_autograd.costreg_apply(net, c, passes, hip_wgrad=wgrad, hip_dgrad=dgrad)
         n_saved = len(out.grad_fn.saved_tensors)
         out.backward(g_out)
         grads = {name: p.grad.clone() for name, p in net.named_parameters()}
@@ -147,3 +143,35 @@ def test_through_the_regularisation_net(hip):
     # the same code runs either way, so on/off is one more sample of the off/off difference: zero where the path is
     # deterministic, else within the factor the parameter gradients above are given
     assert d3 <= 4 * noise3
+
+
+def test_both_switches_reach_costreg_apply_as_arguments(hip, monkeypatch):
+    """A real MVSNet.forward under autograd in bf16 autocast (three 64 x 96 views: a 16 x 24 volume of the 128 depths
+    the builder fixes) with zest_autograd.costreg_apply replaced by a recorder: for all four settings of
+    MVSNet.zest_hip_costreg_wgrad / zest_hip_costreg_dgrad both keyword values equal the attributes, and the forward
+    pass assigns no attribute of cost_reg_2."""
+    import test_generators as tg
+    import zest_autograd
+    import zest_networks as networks
+    x = tg._batch(17, H=64, W=96)
+    imgs, proj, nf = x["images"][:, :3], x["proj_mats"][:, :3], x["near_fars"][0, 0]
+    net = networks.MVSNet().to(DEV).train()
+    calls = []
+
+    def recorder(reg, cost_vol, passes, **switches):
+        calls.append((reg, tuple(cost_vol.shape), passes, switches))
+        return cost_vol[:, :8] * 1.0
+    monkeypatch.setattr(zest_autograd, "costreg_apply", recorder)
+    before = dict(vars(net.cost_reg_2))
+    for wgrad in (False, True):
+        for dgrad in (False, True):
+            net.zest_hip_costreg_wgrad, net.zest_hip_costreg_dgrad = wgrad, dgrad
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                vol = net(imgs, proj, nf, pad=0)[0]
+            assert len(calls) == 1 and tuple(vol.shape) == (1, 8, 128, 16, 24)
+            reg, shape, passes, switches = calls.pop()
+            assert reg is net.cost_reg_2 and shape == (1, 41, 128, 16, 24) and passes == 1
+            assert sorted(switches) == ["hip_dgrad", "hip_wgrad"]
+            assert switches["hip_wgrad"] is wgrad and switches["hip_dgrad"] is dgrad
+    after = vars(net.cost_reg_2)
+    assert list(after) == list(before) and all(after[k] is before[k] for k in before)

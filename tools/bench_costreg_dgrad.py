@@ -2,7 +2,7 @@
 """The data gradient of CostRegNet.conv0 (Conv3d 41 -> 8, 3 x 3 x 3) - the gradient towards the cost volume - in the
 --precision 16 training step at the bench geometry, 128 x 120 x 176 voxels, two ways:
 
-  library      what zest_autograd.CostRegFn's conv0_bwd does for it without the switch: the casts of the output gradient
+  library      what zest_autograd._conv0_bwd does for it without the switch: the casts of the output gradient
                and the weight to bf16, aten.convolution_backward with output_mask [True, False, False] (an uninitialised
                bf16 tensor standing in for the cost volume) and the cast of the result to fp32; measured twice
                (.., library_again) for the spread

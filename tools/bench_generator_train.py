@@ -49,5 +49,6 @@ with profile(activities=[ProfilerActivity.CUDA]) as prof:
 rows = sorted(prof.key_averages(), key=lambda e: -e.device_time_total)
 tot = sum(e.device_time_total for e in rows)
 print("device time %.1f ms" % (tot / 1e3))
+print("kernel launches %d" % sum(e.count for e in rows))
 for e in rows[:14]:
     print("%8.1f us %5.1f%% x%-3d %s" % (e.device_time_total, 100 * e.device_time_total / tot, e.count, e.key[:100]))

@@ -16,7 +16,7 @@
 // mirrored: kz = 2 - dz, ky = 2 - dy, kx = 2 - q) stay in registers: the workgroup packs w into LDS once (coalesced
 // reads of the 35 KB, 2-byte scattered LDS writes), every wave reads its operands, and the space is then used for
 // the strips.  A gather: every element of g_x is written exactly once, no atomics, no zeroing beforehand.
-#include "mlp_engine.cuh"
+#include "costreg_conv0_grad.cuh"
 
 namespace {
 
@@ -29,7 +29,7 @@ constexpr int kSP = kXT + 2;              // pixels of a staged row
 constexpr int kRows = 3 * kIY;
 constexpr int kItems = kRows * kSP;       // staged pixels of a tile (16 bytes each)
 constexpr int kNR = (kItems + 63) / 64;   // staging rounds of a wave
-constexpr int kCO = 8, kCI = 48, kNT = kCI / 16, kTaps = 27;
+constexpr int kNT = kCI / 16;
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kWgCap = 1024;              // two rounds of two workgroups (LDS: 27 KB each) on each of 256 compute units
 constexpr int kStripBytes = kItems * 16;
@@ -53,8 +53,6 @@ inline DgradShape dgrad_shape(int D, int H, int W) {
     s.n_wg = (s.n_tiles + s.tiles_per_wg - 1) / s.tiles_per_wg;
     return s;
 }
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)(pack_bf16(v, 0.f) & 0xFFFFu); }
 
 __global__ __launch_bounds__(kThreads, 2) void dgrad_kernel(const DgradArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[kLds];
@@ -181,11 +179,9 @@ extern "C" int zest_costreg_dgrad_launch_shape(int D, int H, int W, int *n_tiles
 
 extern "C" int zest_costreg_dgrad(const float *g, const float *w, int D, int H, int W, int cin, int cout, float *g_x,
                                   void *stream) {
-    ZEST_CHECK_ARG(cout == kCO, "zest_costreg_dgrad: %d output channels, the kernel is built for %d", cout, kCO);
-    ZEST_CHECK_ARG(cin >= 1 && cin <= kCI, "zest_costreg_dgrad: %d input channels, expected 1 .. %d", cin, kCI);
-    ZEST_CHECK_ARG(dgrad_extents_ok(D, H, W), "zest_costreg_dgrad: bad shape %d x %d x %d", D, H, W);
-    ZEST_CHECK_ARG(g && w && g_x, "zest_costreg_dgrad: null pointer");
-    ZEST_CHECK_ARG(aligned16(g) && aligned16(w) && aligned16(g_x), "zest_costreg_dgrad: g, w and g_x must be 16-byte aligned");
+    if (const int refused = conv0_grad_refusal("zest_costreg_dgrad", cin, cout, dgrad_extents_ok(D, H, W), D, H, W, g && w && g_x,
+                                               aligned16(g) && aligned16(w) && aligned16(g_x), "g, w and g_x"))
+        return refused;
     const DgradShape s = dgrad_shape(D, H, W);
     DgradArgs a{};
     a.g = g, a.w = w, a.g_x = g_x;

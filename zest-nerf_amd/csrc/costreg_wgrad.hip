@@ -14,7 +14,7 @@
 // three share the staged rows.  A unit of work is TY rows of one slice; a workgroup walks a contiguous range of units
 // and writes ONE partial [27][8][48]; wgrad_finish_kernel adds the partials in a fixed order (no float atomics: two
 // calls on the same data give the same bits) and writes g_w [8][cin][27].
-#include "mlp_engine.cuh"
+#include "costreg_conv0_grad.cuh"
 
 namespace {
 
@@ -23,7 +23,7 @@ using namespace zest;
 constexpr int kTY = 4;                    // x rows of a unit
 constexpr int kGR = kTY + 2;              // g rows per slice around them
 constexpr int kKC = 32;                   // voxels of a chunk = k of one MFMA
-constexpr int kCI = 48, kCO = 8, kTaps = 27, kTiles = 14;
+constexpr int kTiles = 14;
 constexpr int kWgCap = 768;               // three workgroups (LDS: 46 KB each) on each of 256 compute units
 constexpr int kPartial = kTaps * kCO * kCI;
 constexpr int kGBlock = 320;              // shorts of one (g row, kx) image: [4 octets][8 co][8 voxels] = 512 B + 128 B, so
@@ -47,8 +47,6 @@ inline WgradShape wgrad_shape(int D, int H, int W) {
     (void)W;
     return s;
 }
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)(pack_bf16(v, 0.f) & 0xFFFFu); }
 
 __global__ __launch_bounds__(kThreads) void wgrad_kernel(const WgradArgs a) {
     __shared__ uint4 xs[kTY * 4 * kCI];                                   // [row][octet][ci] x 8 voxels
@@ -177,11 +175,9 @@ extern "C" size_t zest_costreg_wgrad_work_bytes(int D, int H, int W) {
 
 extern "C" int zest_costreg_wgrad(const float *x, const float *g, int D, int H, int W, int cin, int cout, void *work,
                                   float *g_w, void *stream) {
-    ZEST_CHECK_ARG(cout == kCO, "zest_costreg_wgrad: %d output channels, the kernel is built for %d", cout, kCO);
-    ZEST_CHECK_ARG(cin >= 1 && cin <= kCI, "zest_costreg_wgrad: %d input channels, expected 1 .. %d", cin, kCI);
-    ZEST_CHECK_ARG(wgrad_extents_ok(D, H, W), "zest_costreg_wgrad: bad shape %d x %d x %d", D, H, W);
-    ZEST_CHECK_ARG(x && g && work && g_w, "zest_costreg_wgrad: null pointer");
-    ZEST_CHECK_ARG(aligned16(x) && aligned16(g) && aligned16(work), "zest_costreg_wgrad: x, g and work must be 16-byte aligned");
+    if (const int refused = conv0_grad_refusal("zest_costreg_wgrad", cin, cout, wgrad_extents_ok(D, H, W), D, H, W, x && g && work && g_w,
+                                               aligned16(x) && aligned16(g) && aligned16(work), "x, g and work"))
+        return refused;
     const WgradShape s = wgrad_shape(D, H, W);
     WgradArgs a{};
     a.x = x, a.g = g, a.work = (float *)work;

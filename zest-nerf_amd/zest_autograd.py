@@ -520,50 +520,87 @@ class ProjectRaysFn(Function):
         return dw, dp, None, None, None, None
 
 
-# ------------------------------------------------------------------------------ volume builder: regularisation net
+# ------------------------------------------------------------------------------ volume builder: the two HIP-forward nets
+def _keep_layers(ctx, net, passes, x, raw, pr, mo, params, extra=None):
+    """Keep what the backward pass of a net with a HIP forward reads: its input, every layer's raw output, norm
+    constants and batch moments, the parameters and, if given, one more tensor - always last; ctx remembers whether.
+    ctx.low: torch.bfloat16 on the --precision 16 path (passes == 1: library backward in bf16, as under AMP), else None."""
+    ctx.net, ctx.low, ctx.n, ctx.has_extra = net, (torch.bfloat16 if passes == 1 else None), len(raw), extra is not None
+    ctx.save_for_backward(x, *raw, *pr, *mo, *params, *(() if extra is None else (extra,)))
+
+
+def _kept_layers(ctx):
+    """-> (x, raw, pr, mo, params, extra) as _keep_layers took them (extra: None when none was given)."""
+    t, n = ctx.saved_tensors, ctx.n
+    t, extra = (t[:-1], t[-1]) if ctx.has_extra else (t, None)
+    return t[0], t[1:1 + n], t[1 + n:1 + 2 * n], t[1 + 2 * n:1 + 3 * n], t[1 + 3 * n:], extra
+
+
+def _conv_bwd(g_r, x, w, low, stride, padding, transposed, mask):
+    """The library's convolution backward (no bias, no dilation, one group; 2-D or 3-D by the weight's rank), operands
+    cast to `low` (ctx.low) unless None -> (g_x, g_w) in fp32, None where `mask` = [input, weight, False] does not ask."""
+    if low is not None:
+        g_r, x, w = g_r.to(low), x.to(low), w.to(low)
+    nd = w.dim() - 2
+    g_x, g_w, _ = torch.ops.aten.convolution_backward(g_r, x, w, None, [stride] * nd, [padding] * nd, [1] * nd, transposed,
+                                                      [1 if transposed else 0] * nd, 1, mask)
+    return (g_x.float() if mask[0] else None), (g_w.float() if mask[1] else None)
+
+
+def _norm_bwd(i, g_cl, raw, pr, mo, gam):
+    """Through leaky ReLU and the training-mode batch norm of layer i: one HIP call on the channels-last tensors
+    (zest_costreg_bn_bwd; the library's norm backward has no channels-last kernel - its generic fallback took 7 ms of a
+    40 ms step, the same arithmetic in torch operators as much) -> (g_raw like raw[i], g_gamma, g_beta)."""
+    return zest_hip.costreg_bn_bwd(raw[i], g_cl.contiguous(), pr[i], mo[i], gam[i])   # a view when channels-last already
+
+
+def _conv0_bwd(g_r, cost, w, low, want_x, hip_wgrad, hip_dgrad, cl):
+    """Backward of CostRegNet.conv0, the one layer that reads the cost volume: g_r [1,8,D,H,W] (a view of
+    zest_costreg_bn_bwd's channels-last result) -> (g_cost or None, g_w).  Each gradient comes from its HIP kernel when
+    its switch is on - zest_costreg_wgrad on the kept channels-last cost volume `cl`, zest_costreg_dgrad on the fp32
+    weight - and from ONE library call otherwise, which is left out when nothing remains for it.  For the data
+    gradient alone the library reads no input value, so an uninitialised bf16 tensor of the cost volume's sizes stands in."""
+    mask = [want_x and not hip_dgrad, not hip_wgrad, False]
+    g_cl0 = g_r[0].permute(1, 2, 3, 0)
+    g_x = zest_hip.costreg_dgrad(g_cl0, w)[None] if (want_x and hip_dgrad) else None
+    g_w = zest_hip.costreg_wgrad(cl, g_cl0, cost.shape[1]) if hip_wgrad else None
+    if mask[0] or mask[1]:
+        lib_x, lib_w = _conv_bwd(g_r, cost if mask[1] else torch.empty_like(cost, dtype=low), w, low, 1, 1, False, mask)
+        g_x, g_w = (lib_x if mask[0] else g_x), (lib_w if mask[1] else g_w)
+    return g_x, g_w
+
+
 class CostRegFn(Function):
     """CostRegNet under autograd with its FORWARD on the HIP kernels (csrc/costreg.hip, 1 ms instead of the library's
     8-11 ms): the raw output of every layer, its norm constants and batch moments are kept, and the backward pass
-    walks the U-Net in reverse with the library's own backward operators on them (aten.convolution_backward,
-    aten.native_batch_norm_backward; the leaky ReLU and the skip additions are a few elementwise operations).
-    hip_wgrad (MVSNet.zest_hip_costreg_wgrad; bf16 operands, passes == 1, only - with passes == 3 it changes nothing):
-    the weight gradient of layer 0, the one layer that reads the 41-channel cost volume at full resolution, comes from
-    zest_costreg_wgrad (csrc/costreg_wgrad.hip: fp32 result, not rounded to bf16) and the library is asked for that
-    layer's data gradient only, which needs neither the bf16 copy of the cost volume nor its values.  The price: the
-    padded channels-last copy of the cost volume [D,H,W,48] fp32 that the forward builds is kept until the backward
-    pass, 0.5 GB per volume builder at 128 x 120 x 176.
-    net.zest_hip_dgrad (MVSNet.zest_hip_costreg_dgrad; read in forward, passes == 1 only as well): the data gradient of
-    layer 0 - the gradient towards the cost volume - comes from zest_costreg_dgrad (csrc/costreg_dgrad.hip) on
-    zest_costreg_bn_bwd's channels-last result and the module's fp32 weight: fp32 channel planes, no casts, no
-    transposes, nothing extra kept.  The library is then asked only for what is still missing: the weight gradient
-    without hip_wgrad, nothing with it (no bf16 stand-in for the cost volume either).
-    Inputs after `hip_wgrad`: the ten convolution weights, then (weight, bias) of the ten norms, in layer order."""
+    walks the U-Net in reverse with the library's own convolution backward on them (aten.convolution_backward) and
+    zest_costreg_bn_bwd for norm + leaky ReLU; the skip additions are a few elementwise operations.
+    Two opt-in arguments for layer 0, the one layer that reads the 41-channel cost volume at full resolution
+    (_conv0_bwd); both hold for bf16 operands (passes == 1) only - with passes == 3 they change nothing:
+    hip_wgrad (MVSNet.zest_hip_costreg_wgrad): the weight gradient comes from zest_costreg_wgrad
+    (csrc/costreg_wgrad.hip: fp32 result, not rounded to bf16) and the library is asked for the data gradient only,
+    which needs neither the bf16 copy of the cost volume nor its values.  The price: the padded channels-last copy
+    [D,H,W,48] fp32 that the forward builds is kept until the backward pass, 0.5 GB per builder at 128 x 120 x 176.
+    hip_dgrad (MVSNet.zest_hip_costreg_dgrad): the data gradient - the gradient towards the cost volume - comes from
+    zest_costreg_dgrad (csrc/costreg_dgrad.hip) on zest_costreg_bn_bwd's channels-last result and the module's fp32
+    weight: fp32 channel planes, no casts, no transposes, nothing extra kept.  The library is then asked only for what
+    is still missing: the weight gradient without hip_wgrad, nothing with it (no bf16 stand-in for the cost volume either).
+    Inputs after `hip_dgrad`: the ten convolution weights, then (weight, bias) of the ten norms, in layer order."""
 
     @staticmethod
-    def forward(ctx, cost, net, passes, hip_wgrad, *params):
+    def forward(ctx, cost, net, passes, hip_wgrad, hip_dgrad, *params):
         cl = torch.nn.functional.pad(cost[0].permute(1, 2, 3, 0), (0, zest_hip.COST_CL_CHANNELS - cost.shape[1])).contiguous()
         vol, raw, pr, mo = net.forward_hip(cl, passes, keep=True)
-        ctx.net, ctx.passes, ctx.n = net, passes, len(raw)
-        ctx.hip_wgrad = bool(hip_wgrad) and passes == 1
-        ctx.hip_dgrad = bool(getattr(net, "zest_hip_dgrad", False)) and passes == 1
-        if ctx.hip_wgrad:
-            ctx.save_for_backward(cost, *raw, *pr, *mo, *params, cl)
-        else:
-            ctx.save_for_backward(cost, *raw, *pr, *mo, *params)
+        ctx.hip_wgrad, ctx.hip_dgrad = (bool(s) and passes == 1 for s in (hip_wgrad, hip_dgrad))
+        _keep_layers(ctx, net, passes, cost, raw, pr, mo, params, extra=cl if ctx.hip_wgrad else None)
         return vol
 
     @staticmethod
     def backward(ctx, g_out):
-        t = ctx.saved_tensors
-        n = ctx.n
-        cl = None
-        if ctx.hip_wgrad:
-            t, cl = t[:-1], t[-1]
-        cost, raw, pr, mo, params = t[0], t[1:1 + n], t[1 + n:1 + 2 * n], t[1 + 2 * n:1 + 3 * n], t[1 + 3 * n:]
+        cost, raw, pr, mo, params, cl = _kept_layers(ctx)
+        n, low = ctx.n, ctx.low
         W, gam = params[:n], params[n::2]
-        net = ctx.net
-        bns = [getattr(net, nm).bn for nm, _ in net._HIP_CONVS] + [getattr(net, nm)[1] for nm in net._HIP_UPS]
-        low = torch.bfloat16 if ctx.passes == 1 else None          # the --precision 16 path: library backward in bf16, as under AMP
+        convs, _ = ctx.net.hip_layers()
         cf = lambda x: x.permute(3, 0, 1, 2)[None]                  # [D,H,W,C] -> [1,C,D,H,W] (channels-last memory)
         vec = lambda v: v.view(1, -1, 1, 1, 1)
 
@@ -571,73 +608,35 @@ class CostRegFn(Function):
             return torch.nn.functional.leaky_relu(cf(raw[i]) * vec(pr[i][0]) + vec(pr[i][1]), 0.01)
 
         def norm_bwd(i, g_a):
-            """Through leaky ReLU and the training-mode batch norm of layer i: one HIP call on the channels-last
-            tensors (zest_costreg_bn_bwd; the library's norm backward has no channels-last kernel - its generic
-            fallback took 7 ms of a 40 ms step, the same arithmetic in torch operators as much)."""
-            g_cl = g_a[0].permute(1, 2, 3, 0).contiguous()          # a view when the gradient is channels-last already
-            g_r, g_w, g_b = zest_hip.costreg_bn_bwd(raw[i], g_cl, pr[i], mo[i], gam[i])
-            return cf(g_r), g_w, g_b
+            g_r, gG[i], gB[i] = _norm_bwd(i, g_a[0].permute(1, 2, 3, 0), raw, pr, mo, gam)
+            return cf(g_r)
 
-        def conv_bwd(g_r, x, w, stride, transposed, want_x=True):
-            if low is not None:
-                g_r, x, w = g_r.to(low), x.to(low), w.to(low)
-            g_x, g_w, _ = torch.ops.aten.convolution_backward(g_r, x, w, None, [stride] * 3, [1] * 3, [1] * 3, transposed,
-                                                              [1 if transposed else 0] * 3, 1, [want_x, True, False])
-            return (g_x.float() if want_x else None), g_w.float()
-
-        def conv0_bwd(g_r, want_x):
-            """Layer 0 with hip_wgrad and / or hip_dgrad, on the channels-last tensors (g_r is a view of costreg_bn_bwd's
-            [D,H,W,8] result): the weight gradient from zest_costreg_wgrad on the kept cost volume, the data gradient
-            from zest_costreg_dgrad on the fp32 weight; the library gives the one that is not taken from a kernel - for
-            the data gradient alone it reads no input value, so an uninitialised bf16 tensor of the cost volume's
-            sizes stands in."""
-            g_cl0 = g_r[0].permute(1, 2, 3, 0)
-            g_x = zest_hip.costreg_dgrad(g_cl0, W[0])[None] if (want_x and ctx.hip_dgrad) else None
-            if cl is None:
-                _, g_w, _ = torch.ops.aten.convolution_backward(g_r.to(low), cost.to(low), W[0].to(low), None, [1] * 3, [1] * 3,
-                                                                [1] * 3, False, [0] * 3, 1, [False, True, False])
-                return g_x, g_w.float()
-            g_w = zest_hip.costreg_wgrad(cl, g_cl0, cost.shape[1])
-            if want_x and g_x is None:
-                g_x, _, _ = torch.ops.aten.convolution_backward(g_r.to(low), torch.empty_like(cost, dtype=low), W[0].to(low), None,
-                                                                [1] * 3, [1] * 3, [1] * 3, False, [0] * 3, 1, [True, False, False])
-                g_x = g_x.float()
-            return g_x, g_w
+        def conv_bwd(i, g_r, x):
+            g_x, gW[i] = _conv_bwd(g_r, x, W[i], low, convs[i].stride[0], 1, convs[i].transposed, [True, True, False])
+            return g_x
         gW, gG, gB = [None] * n, [None] * n, [None] * n
         g_out = g_out.contiguous()
         # up path (layers 9, 8, 7 = conv11, conv9, conv7), skip additions on the way
-        g_r, gG[9], gB[9] = norm_bwd(9, g_out)
-        g_x2, gW[9] = conv_bwd(g_r, act(2) + act(8), W[9], 2, True)
-        g_r, gG[8], gB[8] = norm_bwd(8, g_x2)
-        g_x1, gW[8] = conv_bwd(g_r, act(4) + act(7), W[8], 2, True)
-        g_r, gG[7], gB[7] = norm_bwd(7, g_x1)
-        g_a, gW[7] = conv_bwd(g_r, act(6), W[7], 2, True)
-        # down path in reverse (layers 6 .. 0)
-        skip = {4: g_x1, 2: g_x2, 0: g_out}
-        strides = [s for _, s in net._HIP_CONVS]
-        for i in range(6, -1, -1):
+        g_x2 = conv_bwd(9, norm_bwd(9, g_out), act(2) + act(8))
+        g_x1 = conv_bwd(8, norm_bwd(8, g_x2), act(4) + act(7))
+        g_a = conv_bwd(7, norm_bwd(7, g_x1), act(6))
+        # down path in reverse (layers 6 .. 1), then layer 0
+        skip = {4: g_x1, 2: g_x2}
+        for i in range(6, 0, -1):
             if i in skip:
                 g_a = g_a + skip[i]
-            g_r, gG[i], gB[i] = norm_bwd(i, g_a)
-            if i == 0 and (cl is not None or (ctx.hip_dgrad and ctx.needs_input_grad[0])):
-                g_a, gW[0] = conv0_bwd(g_r, ctx.needs_input_grad[0])
-                break
-            x = act(i - 1) if i > 0 else cost
-            g_a, gW[i] = conv_bwd(g_r, x, W[i], strides[i], False, want_x=(i > 0 or ctx.needs_input_grad[0]))
-        grads = list(gW)
-        for i in range(n):
-            grads += [gG[i], gB[i]]
-        return (g_a, None, None, None) + tuple(grads)
+            g_a = conv_bwd(i, norm_bwd(i, g_a), act(i - 1))
+        g_a, gW[0] = _conv0_bwd(norm_bwd(0, g_a + g_out), cost, W[0], low, ctx.needs_input_grad[0], ctx.hip_wgrad,
+                                ctx.hip_dgrad, cl)
+        return (g_a, None, None, None, None, *gW, *(g for pair in zip(gG, gB) for g in pair))
 
 
-def costreg_apply(net, cost_vol, passes, hip_wgrad=False):
-    """CostRegNet(cost_vol [1,41,D,H,W]) -> [1,8,D,H,W] through CostRegFn.  hip_wgrad: see there (opt-in; passes == 1 only)."""
-    convs = [getattr(net, nm).conv for nm, _ in net._HIP_CONVS] + [getattr(net, nm)[0] for nm in net._HIP_UPS]
-    bns = [getattr(net, nm).bn for nm, _ in net._HIP_CONVS] + [getattr(net, nm)[1] for nm in net._HIP_UPS]
-    params = [c.weight for c in convs]
-    for b in bns:
-        params += [b.weight, b.bias]
-    return CostRegFn.apply(cost_vol.float(), net, passes, bool(hip_wgrad), *params)
+def costreg_apply(net, cost_vol, passes, hip_wgrad=False, hip_dgrad=False):
+    """CostRegNet(cost_vol [1,41,D,H,W]) -> [1,8,D,H,W] through CostRegFn.  hip_wgrad, hip_dgrad: layer 0's weight /
+    data gradient from the HIP kernels, see there (opt-in; passes == 1 only)."""
+    convs, bns = net.hip_layers()
+    params = [c.weight for c in convs] + [p for b in bns for p in (b.weight, b.bias)]
+    return CostRegFn.apply(cost_vol.float(), net, passes, bool(hip_wgrad), bool(hip_dgrad), *params)
 
 
 class FeatureFn(Function):
@@ -649,18 +648,15 @@ class FeatureFn(Function):
     @staticmethod
     def forward(ctx, imgs, net, passes, *params):
         feats, raw, pr, mo = net.forward_hip(imgs, passes, keep=True)
-        ctx.net, ctx.passes, ctx.n = net, passes, len(raw)
-        ctx.save_for_backward(imgs, *raw, *pr, *mo, *params)
+        _keep_layers(ctx, net, passes, imgs, raw, pr, mo, params)
         return feats.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, g_feats):
-        t = ctx.saved_tensors
-        n = ctx.n
-        imgs, raw, pr, mo, params = t[0], t[1:1 + n], t[1 + n:1 + 2 * n], t[1 + 2 * n:1 + 3 * n], t[1 + 3 * n:]
+        imgs, raw, pr, mo, params, _ = _kept_layers(ctx)
+        n, low = ctx.n, ctx.low
         W, top_w, gam = params[:n], params[n], params[n + 2::2]
-        convs = [getattr(ctx.net, s_)[i] for s_, i in ctx.net._HIP_LAYERS]
-        low = torch.bfloat16 if ctx.passes == 1 else None
+        layers = ctx.net.hip_layers()
         cf = lambda x: x.permute(0, 3, 1, 2)                       # [N,H,W,C] -> [N,C,H,W] (channels-last memory)
         act = lambda i: torch.nn.functional.leaky_relu(raw[i] * pr[i][0] + pr[i][1], 0.01)
         g2 = g_feats.permute(0, 2, 3, 1).reshape(-1, 32).float()
@@ -669,27 +665,18 @@ class FeatureFn(Function):
         g_a = (g2 @ top_w.view(32, 32).float()).view(raw[n - 1].shape)      # channels-last gradient of the last activation
         gW, gG, gB = [None] * n, [None] * n, [None] * n
         for i in range(n - 1, -1, -1):
-            g_r, gG[i], gB[i] = zest_hip.costreg_bn_bwd(raw[i], g_a.contiguous(), pr[i], mo[i], gam[i])
-            x = cf(act(i - 1)) if i > 0 else imgs
-            k, s_ = convs[i].conv.kernel_size[0], convs[i].conv.stride[0]
-            go, xi, w = cf(g_r), x, W[i]
-            if low is not None:
-                go, xi, w = go.to(low), xi.to(low), w.to(low)
-            g_x, g_w, _ = torch.ops.aten.convolution_backward(go, xi, w, None, [s_] * 2, [k // 2] * 2, [1, 1], False, [0, 0], 1,
-                                                              [i > 0, True, False])
-            gW[i] = g_w.float()
+            g_r, gG[i], gB[i] = _norm_bwd(i, g_a, raw, pr, mo, gam)
+            conv = layers[i].conv
+            g_x, gW[i] = _conv_bwd(cf(g_r), cf(act(i - 1)) if i > 0 else imgs, W[i], low, conv.stride[0],
+                                   conv.kernel_size[0] // 2, False, [i > 0, True, False])
             if i > 0:
-                g_a = g_x.float().permute(0, 2, 3, 1)
-        grads = list(gW) + [g_top_w, g_top_b]
-        for i in range(n):
-            grads += [gG[i], gB[i]]
-        return (None, None, None) + tuple(grads)
+                g_a = g_x.permute(0, 2, 3, 1)
+        return (None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
 
 
 def feature_apply(net, imgs, passes):
     """FeatureNet(imgs [N,3,H,W]) -> [N,32,H/4,W/4] through FeatureFn."""
-    convs = [getattr(net, s_)[i] for s_, i in net._HIP_LAYERS]
-    params = [m.conv.weight for m in convs] + [net.toplayer.weight, net.toplayer.bias]
-    for m in convs:
-        params += [m.bn.weight, m.bn.bias]
+    layers = net.hip_layers()
+    params = ([m.conv.weight for m in layers] + [net.toplayer.weight, net.toplayer.bias]
+              + [p for m in layers for p in (m.bn.weight, m.bn.bias)])
     return FeatureFn.apply(imgs.float(), net, passes, *params)

@@ -1036,16 +1036,25 @@ def _check_stats(stats, cout, who):
         raise RuntimeError("zest_hip.%s: stats %s %s for %d channels" % (who, tuple(stats.shape), stats.dtype, cout))
 
 
+def _check_packed(w_packed, need, who, what):
+    """The packed weights are on the device and exactly as long as the kernel reads them (`what`: the layer, for the text)."""
+    have = w_packed.numel() * w_packed.element_size()
+    if have != int(need) or not w_packed.is_cuda:
+        raise RuntimeError("zest_hip.%s: packed weights of %d bytes, %s take %d" % (who, have, what, need))
+
+
+def _check_pre(pre, cin, who, name="pre"):
+    if pre is not None and (tuple(pre.shape) != (2, cin) or pre.dtype != torch.float32 or not pre.is_contiguous()):
+        raise RuntimeError("zest_hip.%s: %s %s for %d channels" % (who, name, tuple(pre.shape), cin))
+
+
 def costreg_conv(x, pre, w_packed, cout, stride, passes, stats):
     """x [D,H,W,cin] raw channels-last; pre [2,cin] or None; -> raw [Do,Ho,Wo,cout]; stats: costreg_stats(cout)."""
     x = _dev(x, "x")
     D, H, W, cin = x.shape
-    need = int(lib().zest_costreg_packed_bytes(cin, cout, passes))
-    if w_packed.numel() * w_packed.element_size() != need or not w_packed.is_cuda:
-        raise RuntimeError("zest_hip.costreg_conv: packed weights of %d bytes, %d -> %d channels in %d passes take %d"
-                           % (w_packed.numel() * w_packed.element_size(), cin, cout, passes, need))
-    if pre is not None and (tuple(pre.shape) != (2, cin) or pre.dtype != torch.float32 or not pre.is_contiguous()):
-        raise RuntimeError("zest_hip.costreg_conv: pre %s for %d channels" % (tuple(pre.shape), cin))
+    _check_packed(w_packed, lib().zest_costreg_packed_bytes(cin, cout, passes), "costreg_conv",
+                  "%d -> %d channels in %d passes" % (cin, cout, passes))
+    _check_pre(pre, cin, "costreg_conv")
     _check_stats(stats, cout, "costreg_conv")
     o = lambda n: (n - 1) // stride + 1
     out = torch.empty(o(D), o(H), o(W), cout, device=x.device, dtype=torch.float32)
@@ -1059,12 +1068,9 @@ def conv2d_cl(x, pre, w_packed, cout, k, stride, passes, stats):
     on act(norm(x))); stats: costreg_stats(cout)."""
     x = _dev(x, "x")
     N, H, W, cin = x.shape
-    need = int(lib().zest_conv2d_packed_bytes(cin, cout, k, passes))
-    if w_packed.numel() * w_packed.element_size() != need or not w_packed.is_cuda:
-        raise RuntimeError("zest_hip.conv2d_cl: packed weights of %d bytes, %d -> %d channels, k %d, %d passes take %d"
-                           % (w_packed.numel() * w_packed.element_size(), cin, cout, k, passes, need))
-    if pre is not None and (tuple(pre.shape) != (2, cin) or pre.dtype != torch.float32 or not pre.is_contiguous()):
-        raise RuntimeError("zest_hip.conv2d_cl: pre %s for %d channels" % (tuple(pre.shape), cin))
+    _check_packed(w_packed, lib().zest_conv2d_packed_bytes(cin, cout, k, passes), "conv2d_cl",
+                  "%d -> %d channels, k %d, %d passes" % (cin, cout, k, passes))
+    _check_pre(pre, cin, "conv2d_cl")
     _check_stats(stats, cout, "conv2d_cl")
     o = lambda n: (n - 1) // stride + 1
     out = torch.empty(N, o(H), o(W), cout, device=x.device, dtype=torch.float32)
@@ -1078,13 +1084,10 @@ def costreg_deconv(x0, pre0, x1, pre1, w_packed, cout, passes, stats):
     x0 = _dev(x0, "x0")
     D, H, W, cin = x0.shape
     x1 = _dev(x1, "x1", (D, H, W, cin))
-    for nm, t in (("pre0", pre0), ("pre1", pre1)):
-        if t is not None and (tuple(t.shape) != (2, cin) or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise RuntimeError("zest_hip.costreg_deconv: %s %s for %d channels" % (nm, tuple(t.shape), cin))
-    need = int(lib().zest_costreg_deconv_packed_bytes(cin, cout, passes))
-    if w_packed.numel() * w_packed.element_size() != need or not w_packed.is_cuda:
-        raise RuntimeError("zest_hip.costreg_deconv: packed weights of %d bytes, %d -> %d channels in %d passes take %d"
-                           % (w_packed.numel() * w_packed.element_size(), cin, cout, passes, need))
+    _check_pre(pre0, cin, "costreg_deconv", "pre0")
+    _check_pre(pre1, cin, "costreg_deconv", "pre1")
+    _check_packed(w_packed, lib().zest_costreg_deconv_packed_bytes(cin, cout, passes), "costreg_deconv",
+                  "%d -> %d channels in %d passes" % (cin, cout, passes))
     _check_stats(stats, cout, "costreg_deconv")
     out = torch.empty(2 * D, 2 * H, 2 * W, cout, device=x0.device, dtype=torch.float32)
     _check(lib().zest_costreg_deconv_fwd(_ptr(x0), _ptr(pre0), _ptr(x1), _ptr(pre1), _ptr(w_packed), cin, cout, passes,
@@ -1141,38 +1144,52 @@ def costreg_wgrad_work_floats(D, H, W):
     return n // 4
 
 
+def _conv0_grad_operands(who, operands, cin, same_extents=False):
+    """The checks costreg_wgrad and costreg_dgrad share.  operands: two of (name, tensor, layout as text, test of rank and
+    fixed sizes).  dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device - the first
+    operand's, which is returned.  same_extents: the two agree in their three leading sizes."""
+    for nm, t, what, ok in operands:
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
+                               % (who, nm, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
+                                  if torch.is_tensor(t) else type(t).__name__))
+    (nm0, t0), (nm1, t1) = operands[0][:2], operands[1][:2]
+    if same_extents and tuple(t1.shape[:3]) != tuple(t0.shape[:3]):
+        raise RuntimeError("%s: %s %s against %s %s" % (who, nm1, tuple(t1.shape), nm0, tuple(t0.shape)))
+    if not 1 <= cin <= COST_CL_CHANNELS:
+        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
+    for nm, t in ((nm0, t0), (nm1, t1)):
+        if not t.is_cuda or t.device != t0.device:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
+    return t0.device
+
+
+def _conv0_grad_out(who, out, shape, device):
+    """The caller's result buffer, checked, or a fresh one."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    if (not torch.is_tensor(out) or out.device != device or out.dtype != torch.float32 or not out.is_contiguous()
+            or tuple(out.shape) != shape):
+        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, shape, device))
+    return out
+
+
 def costreg_wgrad(x_cl, g_cl, cin, work=None, out=None):
     """Weight gradient of CostRegNet.conv0: x_cl [D,H,W,48] (the padded channels-last cost volume of the forward; channels
     from `cin` on are not read into the result), g_cl [D,H,W,8] (costreg_bn_bwd's g_raw) -> g_w [8,cin,3,3,3] fp32.
     bf16-rounded operands, fp32 accumulation, no atomics.  work / out: the caller's buffers (costreg_wgrad_work_floats
     fp32 elements, 16-byte aligned; [8,cin,3,3,3]) instead of fresh ones."""
-    who = "zest_hip.costreg_wgrad"
-    # dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device
-    for nm, t, ch in (("x_cl", x_cl, COST_CL_CHANNELS), ("g_cl", g_cl, 8)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4 or t.shape[3] != ch:
-            raise RuntimeError("%s: %s must be a contiguous fp32 tensor [D,H,W,%d], got %s"
-                               % (who, nm, ch, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
-                                  if torch.is_tensor(t) else type(t).__name__))
+    who, cin = "zest_hip.costreg_wgrad", int(cin)
+    cl = lambda ch: ("[D,H,W,%d]" % ch, lambda t: t.dim() == 4 and t.shape[3] == ch)
+    dev = _conv0_grad_operands(who, (("x_cl", x_cl) + cl(COST_CL_CHANNELS), ("g_cl", g_cl) + cl(8)), cin, same_extents=True)
     D, H, W, _ = x_cl.shape
-    if tuple(g_cl.shape[:3]) != (D, H, W):
-        raise RuntimeError("%s: g_cl %s against x_cl %s" % (who, tuple(g_cl.shape), tuple(x_cl.shape)))
-    cin = int(cin)
-    if not 1 <= cin <= COST_CL_CHANNELS:
-        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
-    for nm, t in (("x_cl", x_cl), ("g_cl", g_cl)):
-        if not t.is_cuda or t.device != x_cl.device:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
     need = costreg_wgrad_work_floats(D, H, W)
     if work is None:
-        work = torch.empty(need, device=x_cl.device, dtype=torch.float32)
-    elif (work.device != x_cl.device or work.dtype != torch.float32 or not work.is_contiguous() or work.numel() != need
+        work = torch.empty(need, device=dev, dtype=torch.float32)
+    elif (work.device != dev or work.dtype != torch.float32 or not work.is_contiguous() or work.numel() != need
           or work.data_ptr() % 16):
-        raise RuntimeError("%s: work must be %d contiguous fp32 elements on %s, 16-byte aligned" % (who, need, x_cl.device))
-    if out is None:
-        out = torch.empty(8, cin, 3, 3, 3, device=x_cl.device, dtype=torch.float32)
-    elif (out.device != x_cl.device or out.dtype != torch.float32 or not out.is_contiguous()
-          or tuple(out.shape) != (8, cin, 3, 3, 3)):
-        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, (8, cin, 3, 3, 3), x_cl.device))
+        raise RuntimeError("%s: work must be %d contiguous fp32 elements on %s, 16-byte aligned" % (who, need, dev))
+    out = _conv0_grad_out(who, out, (8, cin, 3, 3, 3), dev)
     _check(lib().zest_costreg_wgrad(_ptr(x_cl), _ptr(g_cl), D, H, W, cin, 8, _ptr(work), _ptr(out), _stream(x_cl)),
            "zest_costreg_wgrad")
     return out
@@ -1193,25 +1210,12 @@ def costreg_dgrad(g_cl, weight, out=None):
     own, cin 1 .. 48) -> g_x [cin,D,H,W] fp32 channel planes.  bf16-rounded operands, fp32 accumulation, every element
     written once, no atomics.  out: the caller's [cin,D,H,W] buffer instead of a fresh one."""
     who = "zest_hip.costreg_dgrad"
-    # dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device
-    for nm, t, what, ok in (("g_cl", g_cl, "[D,H,W,8]", lambda t: t.dim() == 4 and t.shape[3] == 8),
-                            ("weight", weight, "[8,cin,3,3,3]", lambda t: t.dim() == 5 and t.shape[0] == 8 and tuple(t.shape[2:]) == (3, 3, 3))):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
-            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
-                               % (who, nm, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
-                                  if torch.is_tensor(t) else type(t).__name__))
+    operands = (("g_cl", g_cl, "[D,H,W,8]", lambda t: t.dim() == 4 and t.shape[3] == 8),
+                ("weight", weight, "[8,cin,3,3,3]", lambda t: t.dim() == 5 and t.shape[0] == 8 and tuple(t.shape[2:]) == (3, 3, 3)))
+    cin = int(weight.shape[1]) if torch.is_tensor(weight) and weight.dim() == 5 else 0    # anything else is refused before cin is looked at
+    dev = _conv0_grad_operands(who, operands, cin)
     D, H, W, _ = g_cl.shape
-    cin = int(weight.shape[1])
-    if not 1 <= cin <= COST_CL_CHANNELS:
-        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
-    for nm, t in (("g_cl", g_cl), ("weight", weight)):
-        if not t.is_cuda or t.device != g_cl.device:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
-    if out is None:
-        out = torch.empty(cin, D, H, W, device=g_cl.device, dtype=torch.float32)
-    elif (not torch.is_tensor(out) or out.device != g_cl.device or out.dtype != torch.float32 or not out.is_contiguous()
-          or tuple(out.shape) != (cin, D, H, W)):
-        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, (cin, D, H, W), g_cl.device))
+    out = _conv0_grad_out(who, out, (cin, D, H, W), dev)
     _check(lib().zest_costreg_dgrad(_ptr(g_cl), _ptr(weight), D, H, W, cin, 8, _ptr(out), _stream(g_cl)),
            "zest_costreg_dgrad")
     return out

@@ -395,6 +395,21 @@ def _hip_norm(bn):
     return isinstance(bn, ActivatedBatchNorm) and bn.activation == "leaky_relu" and abs(bn.activation_param - 0.01) < 1e-12
 
 
+def _layer_slabs(chans, keep, device):
+    """Per-layer views of three allocations for the layers of `chans` output channels: the batch-statistics tables
+    [rows,2,C] float64 (zest_hip.costreg_stats), the norm constants [2,C] and - with keep, else None - the batch
+    moments [2,C], both fp32 -> (st, pr, mo), a list each."""
+    offs = [2 * sum(chans[:i]) for i in range(len(chans) + 1)]
+    rows = zest_hip.costreg_stat_rows()
+    stats_all = torch.empty(rows * offs[-1], device=device, dtype=torch.float64)
+    pre_all = torch.empty(offs[-1], device=device, dtype=torch.float32)
+    mom_all = torch.empty(offs[-1], device=device, dtype=torch.float32) if keep else None
+    st = [stats_all[rows * offs[i]:rows * offs[i + 1]].view(rows, 2, c) for i, c in enumerate(chans)]
+    pr = [pre_all[offs[i]:offs[i + 1]].view(2, c) for i, c in enumerate(chans)]
+    mo = [mom_all[offs[i]:offs[i + 1]].view(2, c) if keep else None for i, c in enumerate(chans)]
+    return st, pr, mo
+
+
 class ConvBnReLU(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, pad=1,
                  norm_act=ActivatedBatchNorm):
@@ -439,8 +454,12 @@ class FeatureNet(nn.Module):
     _HIP_SHAPES = ((3, 8, 3, 1), (8, 8, 3, 1), (8, 16, 5, 2), (16, 16, 3, 1), (16, 16, 3, 1), (16, 32, 5, 2), (32, 32, 3, 1),
                    (32, 32, 3, 1))
 
+    def hip_layers(self):
+        """The eight Conv + norm + activation modules of the HIP path, in layer order."""
+        return [getattr(self, s)[i] for s, i in self._HIP_LAYERS]
+
     def hip_supported(self):
-        convs = [getattr(self, s)[i] for s, i in self._HIP_LAYERS]
+        convs = self.hip_layers()
         shapes = tuple((m.conv.in_channels, m.conv.out_channels, m.conv.kernel_size[0], m.conv.stride[0]) for m in convs)
         top = self.toplayer
         return (shapes == self._HIP_SHAPES and all(_hip_norm(m.bn) for m in convs) and top.kernel_size == (1, 1)
@@ -449,25 +468,17 @@ class FeatureNet(nn.Module):
     def forward_hip(self, imgs, passes=3, keep=False):
         """imgs [N,3,H,W] -> top-level features, channels-last [N,H/4,W/4,32] (what the plane sweep reads), no graph.
         keep: also the raw output, norm constants and batch moments of every layer (zest_autograd.FeatureFn)."""
-        convs = [getattr(self, s)[i] for s, i in self._HIP_LAYERS]
+        convs = self.hip_layers()
         packs = _cached_packs(self, passes, [m.conv.weight for m in convs],
                               lambda: [pack_conv_weights(m.conv.weight, passes) for m in convs])
         chans = [m.bn.num_features for m in convs]
-        offs = [0]
-        for c in chans:
-            offs.append(offs[-1] + 2 * c)
-        rows, dev = zest_hip.costreg_stat_rows(), imgs.device
-        stats_all = torch.empty(rows * offs[-1], device=dev, dtype=torch.float64)
-        pre_all = torch.empty(offs[-1], device=dev, dtype=torch.float32)
-        mom_all = torch.empty(offs[-1], device=dev, dtype=torch.float32) if keep else None
+        st, pr, mo = _layer_slabs(chans, keep, imgs.device)
         x = torch.nn.functional.pad(imgs.float().permute(0, 2, 3, 1), (0, 5)).contiguous()        # [N,H,W,8]
-        pre, raw, pr, mo = None, [], [], []
+        pre, raw = None, []
         for i, m in enumerate(convs):
-            st = stats_all[rows * offs[i]:rows * offs[i + 1]].view(rows, 2, chans[i])
-            x = zest_hip.conv2d_cl(x, pre, packs[i], chans[i], m.conv.kernel_size[0], m.conv.stride[0], passes, st)
-            mom = mom_all[offs[i]:offs[i + 1]].view(2, chans[i]) if keep else None
-            pre = zest_hip.costreg_bn(st, x.numel() // chans[i], m.bn, m.bn.training, pre_all[offs[i]:offs[i + 1]].view(2, chans[i]), mom)
-            raw.append(x), pr.append(pre), mo.append(mom)
+            x = zest_hip.conv2d_cl(x, pre, packs[i], chans[i], m.conv.kernel_size[0], m.conv.stride[0], passes, st[i])
+            pre = zest_hip.costreg_bn(st[i], x.numel() // chans[i], m.bn, m.bn.training, pr[i], mo[i])
+            raw.append(x)
         act = torch.nn.functional.leaky_relu(x * pre[0] + pre[1], 0.01)
         top = self.toplayer
         bias = top.bias if top.bias is not None else act.new_zeros(32)
@@ -502,18 +513,21 @@ class CostRegNet(nn.Module):
         up = lambda i, o: nn.Sequential(
             nn.ConvTranspose3d(i, o, 3, padding=1, output_padding=1, stride=2, bias=False), norm_act(o))
         self.conv7, self.conv9, self.conv11 = up(64, 32), up(32, 16), up(16, 8)
-        # opt-in, set by MVSNet.forward from its zest_hip_costreg_dgrad: zest_autograd.CostRegFn takes conv0's data
-        # gradient from the HIP kernel (csrc/costreg_dgrad.hip; bf16 operands, passes == 1, only)
-        self.zest_hip_dgrad = False
 
     # ---- HIP path, no autograd (csrc/costreg.hip): channels-last tensors, a layer's norm + activation applied by
     # the layer that reads it, batch statistics from the convolution kernels themselves
     _HIP_CONVS = (("conv0", 1), ("conv1", 2), ("conv2", 1), ("conv3", 2), ("conv4", 1), ("conv5", 2), ("conv6", 1))
     _HIP_UPS = ("conv7", "conv9", "conv11")
 
+    def hip_layers(self):
+        """-> (convolutions, norms) of the HIP path: the seven of the way down, then the three transposed ones, in the
+        order of forward_hip's `raw`."""
+        down, ups = [getattr(self, n) for n, _ in self._HIP_CONVS], [getattr(self, n) for n in self._HIP_UPS]
+        return [m.conv for m in down] + [m[0] for m in ups], [m.bn for m in down] + [m[1] for m in ups]
+
     def hip_supported(self):
         """The HIP kernels cover the reference's layer shapes with leaky-ReLU(0.01) norms."""
-        bns = [getattr(self, n).bn for n, _ in self._HIP_CONVS] + [getattr(self, n)[1] for n in self._HIP_UPS]
+        bns = self.hip_layers()[1]
         return (self.conv0.conv.in_channels <= zest_hip.COST_CL_CHANNELS and self.conv0.conv.out_channels == 8
                 and all(_hip_norm(b) for b in bns))
 
@@ -550,16 +564,6 @@ class CostRegNet(nn.Module):
         parts = [hi] if passes == 1 else [hi, (out - hi.float()).to(torch.bfloat16)]
         return torch.stack(parts, 5).contiguous().view(torch.int16).view(-1)       # [8,2,2,ch2,nt,parts,64,8]
 
-    def _hip_packs(self, passes):
-        ws = [getattr(self, n).conv.weight for n, _ in self._HIP_CONVS] + [getattr(self, n)[0].weight for n in self._HIP_UPS]
-
-        def build():
-            packs = {n: pack_conv_weights(getattr(self, n).conv.weight, passes) for n, _ in self._HIP_CONVS}
-            for n in self._HIP_UPS:
-                packs[n] = self._pack_deconv(getattr(self, n)[0].weight, passes)
-            return packs
-        return _cached_packs(self, passes, ws, build)
-
     def forward_hip(self, cost_cl, passes=3, keep=False):
         """cost_cl [D,H,W,48] channels-last (zest_hip.volume_cost_cl) -> encoding volume [1,8,D,H,W], no graph.
         passes 3: split-bf16 operands (16 significant bits); 1: bf16 operands (the --precision 16 path).  Norms in
@@ -569,32 +573,24 @@ class CostRegNet(nn.Module):
         D, H, W, _ = cost_cl.shape
         if D % 8 or H % 8 or W % 8:
             raise RuntimeError("CostRegNet.forward_hip: volume %dx%dx%d is not a multiple of 8 per axis" % (D, H, W))
-        packs = self._hip_packs(passes)
-        bns = [getattr(self, n).bn for n, _ in self._HIP_CONVS] + [getattr(self, n)[1] for n in self._HIP_UPS]
+        convs, bns = self.hip_layers()
+        pack = lambda c: (self._pack_deconv if c.transposed else pack_conv_weights)(c.weight, passes)
+        packs = _cached_packs(self, passes, [c.weight for c in convs], lambda: [pack(c) for c in convs])
         chans = [b.num_features for b in bns]
-        offs = [0]
-        for c in chans:
-            offs.append(offs[-1] + 2 * c)
-        rows = zest_hip.costreg_stat_rows()
-        stats_all = torch.empty(rows * offs[-1], device=cost_cl.device, dtype=torch.float64)
-        pre_all = torch.empty(offs[-1], device=cost_cl.device, dtype=torch.float32)
-        st = [stats_all[rows * offs[i]:rows * offs[i + 1]].view(rows, 2, c) for i, c in enumerate(chans)]
-        pr = [pre_all[offs[i]:offs[i + 1]].view(2, c) for i, c in enumerate(chans)]
-        mom_all = torch.empty(offs[-1], device=cost_cl.device, dtype=torch.float32) if keep else None
-        mo = [mom_all[offs[i]:offs[i + 1]].view(2, c) if keep else None for i, c in enumerate(chans)]
+        st, pr, mo = _layer_slabs(chans, keep, cost_cl.device)
         norm = lambda i, t: zest_hip.costreg_bn(st[i], t.numel() // chans[i], bns[i], bns[i].training, pr[i], mo[i])
         raw, x, pre = [], cost_cl, None
-        for i, (name, stride) in enumerate(self._HIP_CONVS):
-            x = zest_hip.costreg_conv(x, pre, packs[name], chans[i], stride, passes, st[i])
+        for i, (_, stride) in enumerate(self._HIP_CONVS):
+            x = zest_hip.costreg_conv(x, pre, packs[i], chans[i], stride, passes, st[i])
             pre = norm(i, x)
             raw.append(x)
-        up = zest_hip.costreg_deconv(raw[6], pr[6], None, None, packs["conv7"], chans[7], passes, st[7])
+        up = zest_hip.costreg_deconv(raw[6], pr[6], None, None, packs[7], chans[7], passes, st[7])
         norm(7, up)
         raw.append(up)
-        up = zest_hip.costreg_deconv(raw[4], pr[4], up, pr[7], packs["conv9"], chans[8], passes, st[8])
+        up = zest_hip.costreg_deconv(raw[4], pr[4], up, pr[7], packs[8], chans[8], passes, st[8])
         norm(8, up)
         raw.append(up)
-        up = zest_hip.costreg_deconv(raw[2], pr[2], up, pr[8], packs["conv11"], chans[9], passes, st[9])
+        up = zest_hip.costreg_deconv(raw[2], pr[2], up, pr[8], packs[9], chans[9], passes, st[9])
         norm(9, up)
         raw.append(up)
         vol = zest_hip.costreg_out(raw[0], pr[0], up, pr[9])
@@ -719,10 +715,10 @@ class MVSNet(nn.Module):
             # backward: HIP norm kernels + the library's convolution backward on the kept raw outputs
             import zest_autograd
             # zest_hip_costreg_wgrad (opt-in, --precision 16 only): the first layer's weight gradient in HIP as well;
-            # zest_hip_costreg_dgrad (likewise): its data gradient - the switch travels on the module
-            self.cost_reg_2.zest_hip_dgrad = bool(getattr(self, "zest_hip_costreg_dgrad", False))
+            # zest_hip_costreg_dgrad (likewise): its data gradient
             volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes,
-                                                      hip_wgrad=bool(getattr(self, "zest_hip_costreg_wgrad", False)))
+                                                      hip_wgrad=bool(getattr(self, "zest_hip_costreg_wgrad", False)),
+                                                      hip_dgrad=bool(getattr(self, "zest_hip_costreg_dgrad", False)))
         else:
             volume_feat, _ = self.cost_reg_2(cost_vol)
         volume_feat = volume_feat.reshape(1, -1, *volume_feat.shape[2:])
@@ -762,12 +758,9 @@ class _Generator(nn.Module):
             if (not train and getattr(self.args, "zest_graph_builders", True) and isinstance(net, MVSNet)
                     and net.feature.hip_supported() and net.hip_path(imgs, self.args.pad)):
                 return self._volume_replayed(net, imgs, proj_mats, near_far)
-            if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_train", None) is not None:
-                net.zest_hip_costreg_train = bool(self.args.zest_hip_costreg_train)       # the caller's choice, else MVSNet's default
-            if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_wgrad", None) is not None:
-                net.zest_hip_costreg_wgrad = bool(self.args.zest_hip_costreg_wgrad)
-            if train and isinstance(net, MVSNet) and getattr(self.args, "zest_hip_costreg_dgrad", None) is not None:
-                net.zest_hip_costreg_dgrad = bool(self.args.zest_hip_costreg_dgrad)
+            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad"):
+                if train and isinstance(net, MVSNet) and getattr(self.args, name, None) is not None:
+                    setattr(net, name, bool(getattr(self.args, name)))      # the caller's choice, else MVSNet's default
             return net(imgs, proj_mats, near_far, pad=self.args.pad)[0].float()
 
     def _volume_replayed(self, net, imgs, proj_mats, near_far):

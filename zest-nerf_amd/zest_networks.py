@@ -134,6 +134,27 @@ class _MlpBase(nn.Module):
         written for the shipped shape; other depths / widths / skips run exact fp32 products."""
         return prec if self.default_shape else zest_hip.PREC_F32
 
+    def _param_list(self):
+        """The (name, Parameter) pairs of named_parameters(), cached with the tree they were read from: the parameter and
+        child tables of this module and every module below it, and the objects they held.  Each use compares those
+        objects by identity and the tables' sizes (a few dozen dictionary look-ups, no walk of the tree), so a parameter
+        or a leaf replaced anywhere below - `net.alpha_linear.weight = ...`, `net.pts_linears[0] = ...`,
+        `load_state_dict(assign=True)` - rebuilds the list, not only an assignment on this module itself."""
+        ent = self.__dict__.get("_zest_params")
+        if ent is not None:
+            for d, k, obj in ent[1]:
+                if d.get(k) is not obj:
+                    break
+            else:
+                if [len(d) for d in ent[2]] == ent[3]:      # nothing was added either
+                    return ent[0]
+        tables = [d for m in self.modules() for d in (m._parameters, m._modules)]
+        held = tuple((d, k, obj) for d in tables for k, obj in d.items())
+        if self.__dict__.get("_packed"):
+            self._packed.clear()        # packed from other objects: a new one may sit at a freed one's address and version
+        ent = self.__dict__["_zest_params"] = (tuple(self.named_parameters()), held, tables, [len(d) for d in tables])
+        return ent[0]
+
     def effective_parameters(self, time_codes=None):
         """{name: tensor} of the 63/84-channel net the kernels run.  Without time-code channels these
         are the parameters themselves.  With them (in_ch_time = T > 0) `time_codes` ([T] or [1,T], the
@@ -142,10 +163,7 @@ class _MlpBase(nn.Module):
             layer 5:  W5 [256, P+T+256]  -> W5[:, :P] | W5[:, P+T:],  b5 + W5[:, P:P+T] sigmoid(tc)
         (layer i+1 for each i in skips; the skip layer's input is [point | time code | h], networks.py:182).  Plain torch ops: under
         autograd the gradients reach the original parameters and the code."""
-        params = self.__dict__.get("_zest_params")
-        if params is None:
-            params = self.__dict__["_zest_params"] = tuple(self.named_parameters())
-        named = dict(params)
+        named = dict(self._param_list())
         T, P = self.in_ch_time, self.in_ch_pe
         if T == 0:
             if time_codes is not None:
@@ -172,13 +190,13 @@ class _MlpBase(nn.Module):
         (name, Parameter) list is cached - walking the module tree costs more host time than a
         1024-ray launch.  desc: a variant descriptor of the same parameters (forward_alpha), packed and
         cached apart."""
-        params = self.__dict__.get("_zest_params")
-        if params is None:
-            params = self.__dict__["_zest_params"] = tuple(self.named_parameters())
+        params = self._param_list()
         stamp = tuple((p.data_ptr(), p._version) for _, p in params)
         key = precision if desc is None else (precision, desc.use_feat, desc.net_type, desc.head)
         hit = self._packed.get(key)
-        fresh = hit is not None and hit[0] == stamp
+        # whether a code was folded in is part of what the entry is valid for: a call without one on an entry packed
+        # with one takes the miss path, where effective_parameters raises for a net with time-code channels
+        fresh = hit is not None and hit[0] == stamp and (hit[2] is None) == (time_codes is None)
         if fresh and time_codes is not None:
             # The frame's code is folded into the packed biases, so it is part of what the entry is valid for.
             # Its address and version counter do not identify it: the reference's callers build
@@ -382,8 +400,9 @@ def pack_conv_weights(w, passes):
 
 
 def _cached_packs(module, passes, weights, build):
-    """Packed weights of `module`, rebuilt when a weight tensor is replaced or modified in place."""
-    key = (passes,) + tuple((w._version, str(w.device)) for w in weights)
+    """Packed weights of `module`, rebuilt when a weight tensor is replaced, modified in place or given other storage
+    (`w.data = ...`, `.double().float()`: same object, same version counter, another address)."""
+    key = (passes,) + tuple((w.data_ptr(), w._version, str(w.device)) for w in weights)
     cache = module.__dict__.get("_zest_packs")
     # the tensors themselves are compared through weak references (an id() or an address can be recycled)
     if cache is None or cache[0] != key or len(cache[2]) != len(weights) or any(r() is not w for r, w in zip(cache[2], weights)):
@@ -769,10 +788,17 @@ class _Generator(nn.Module):
         call with a given net, shapes and weights runs it directly and then RECORDS it as a HIP graph (recording
         executes nothing: the norms' running estimates advance once per call, as without the graph); later calls
         copy their inputs into the graph's buffers and replay it.  The volume is returned as a copy."""
-        params = list(net.parameters())
+        # The recorded kernels hold ADDRESSES: of every weight, gamma and beta, and of the norms' running estimates and
+        # step counters (read in eval mode, written with batch statistics).  So the entry is valid for these tensor
+        # objects (weak references) at these addresses; for the parameters also at these version counters, since their
+        # packed copies are part of the recording.  The buffers' counters are left out: a replay reads and writes the
+        # buffers themselves, and does not move a counter.
+        weights = list(net.parameters())
+        params = weights + list(net.buffers())
         norms = tuple((m.training, m.eps, m.momentum) for m in net.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm))
         key = (tuple(imgs.shape), tuple(proj_mats.shape), imgs.dtype, self.args.pad, torch.is_autocast_enabled(), norms,
-               str(imgs.device), getattr(net, "zest_hip_costreg", True), tuple(p._version for p in params))
+               str(imgs.device), getattr(net, "zest_hip_costreg", True), tuple(p._version for p in weights),
+               tuple(p.data_ptr() for p in params))
         graphs = self.__dict__.setdefault("_zest_builder_graphs", {})
         for k in [k for k, e in graphs.items() if e["net"]() is None]:
             del graphs[k]                                   # a builder that no longer exists: free its graph and buffers
@@ -790,6 +816,9 @@ class _Generator(nn.Module):
         with torch.cuda.graph(ent["graph"]):
             ent["out"] = net(ent["imgs"], ent["proj"], ent["near_far"], pad=self.args.pad)[0].float()
         torch.cuda.current_stream(imgs.device).wait_stream(cur)
+        # the recording reads the packed operands that _cached_packs held while it was made; a direct forward_hip with
+        # another `passes` replaces them in the modules, so the entry keeps them alive for as long as it can be replayed
+        ent["packs"] = [m.__dict__.get("_zest_packs") for m in (net.feature, net.cost_reg_2)]
         graphs[id(net)] = ent
         return out
 

@@ -289,6 +289,14 @@ __device__ __forceinline__ int feat_col_of(int jb, int rt, int r, int grp, int V
 }
 
 // ------------------------------------------------------------------------------ finishing kernel
+// Floats per sample row of the finishing kernel's LDS image of g_x: every point and feature column an instance can
+// have (63 | 84 point channels, 16 feature channels per feature unit), odd for the bank spread, and 113 where that is
+// enough.  (113 for every instance let a net with more than 113 point + feature columns - 84 + 32 and up - write the
+// tail of a row over the head of the next one, and the last row of a wave over the first of the next wave.)
+constexpr int finish_gx_stride(int nt_pts, int nt_feat) {
+    const int cols = (nt_pts == 4 ? 63 : 84) + 16 * nt_feat;
+    return cols < 113 ? 113 : (cols | 1);
+}
 // Per block of 32 samples, one wave, everything straight from global memory / L2 (no ring):
 //   * point-encoding gradient: the two side-buffer contributions (layers 5 and 0) are added and scattered
 //     into the point columns of g_x through the position map;
@@ -309,7 +317,7 @@ __global__ __launch_bounds__(256) void train16_finish_kernel(
     // The point and feature columns of the block's 32 rows of g_x are assembled in LDS (row = sample) and written
     // out as contiguous 256-byte runs: straight from the accumulators every lane writes another row, 64 cache lines
     // per store instruction (12 % of the kernel).
-    constexpr int kGxStride = 113;                                 // floats per sample row in LDS (>= 84 + 24, odd)
+    constexpr int kGxStride = finish_gx_stride(NT_PTS, NT_FEAT);   // floats per sample row in LDS
     __shared__ float gx_lds[4][32 * kGxStride];
     float *gx_t = gx_lds[threadIdx.x >> 6];
     float *gx_row[CB];
@@ -583,6 +591,8 @@ extern "C" int zest_mlp_train16_bwd(const zest_mlp_desc *desc, const void *packe
         const long long n_blocks = ((long long)M + 31) / 32;
         const uint4 *tail = (const uint4 *)packed_bwd + (size_t)zest::bwd_stream_units_of(d) * 64;
 #define ZEST_FIN(NTP, NTF)                                                                                       \
+    ZEST_CHECK_ARG(P + F <= finish_gx_stride(NTP, NTF), "zest_mlp_train16_bwd: %d point + feature columns, finishing kernel holds %d", \
+                   P + F, finish_gx_stride(NTP, NTF));                                                           \
     hipLaunchKernelGGL((train16_finish_kernel<NTP, NTF>), dim3(zest_div_up(n_blocks, 4)), dim3(256), 0, st, x, M, P, F, \
                        C_in, tail, stash_tiles, grad, (const float4 *)pts_side, t->map_pts, t->map_feat, g_x)
         const int key = t->fwd.nt_pts * 10 + (mod ? t->fwd.nt_feat : 0);

@@ -1548,11 +1548,14 @@ def mlp_train16_pack_bwd(desc, params):
     return packed
 
 
-def mlp_train16_fwd(desc, packed_fwd, x):
-    """x [M, C_in] -> out [M, C_out], stash (opaque: layer outputs as bf16 operand tiles + ReLU masks)."""
+def mlp_train16_fwd(desc, packed_fwd, x, stash=None):
+    """x [M, C_in] -> out [M, C_out], stash (opaque: layer outputs as bf16 operand tiles + ReLU masks).
+    `stash`: a buffer of an earlier call to reuse if it is large enough (as `work` of mlp_train16_bwd)."""
     x = _mlp_rows(desc, x)
     M = x.numel() // x.shape[-1]
-    stash = torch.empty(int(lib().zest_mlp_train16_stash_bytes(C.byref(desc), M)), device=x.device, dtype=torch.uint8)
+    need = int(lib().zest_mlp_train16_stash_bytes(C.byref(desc), M))
+    if stash is None or stash.numel() < need:
+        stash = torch.empty(need, device=x.device, dtype=torch.uint8)
     out = torch.empty(*x.shape[:-1], desc.out_ch, device=x.device, dtype=torch.float32)
     _check(lib().zest_mlp_train16_fwd(C.byref(desc), _ptr(packed_fwd), _ptr(x), M, _ptr(stash), _ptr(out), _stream(x)),
            "zest_mlp_train16_fwd")

@@ -356,6 +356,14 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
     // both nets are read from their inference streams (mlp_plan.h: feature_linear folded into the view layer)
     constexpr int UNITS_S = stream_units(4, NT_FEAT_S, NP, true), UNITS_D = DYN ? stream_units(6, NT_FEAT_D, NP, true) : 0;
     using Ring = RingTiles<kFusedWaves, UNITS_S, UNITS_D>;
+    // Weight-tile window of the engine (mlp_engine.cuh, engine_layer).  Deep (kPrefetchLone) in the 16-bit kernels
+    // without features, which have the registers (190 / 203 VGPRs at depth 3, 202 / 219 now).  Continuous across row
+    // blocks wherever it costs no scratch: every 16-bit kernel and the split-fp16 kernels without features (the
+    // split-fp16 feature kernels, at 249-256 VGPRs, gain 16-36 B of scratch with it).  Measured per family in
+    // profiles/ring_protocol_parent_vs_child.txt.
+    constexpr bool FEATURELESS = !MOD_S && !MOD_D;
+    constexpr int PF = (NP == 1 && FEATURELESS) ? kPrefetchLone : kPrefetch;
+    constexpr bool CONT = NP == 1 || FEATURELESS;
     // LDS: weight ring | cameras of both nets | per-lane (z, dist) of the pass's samples | an unused gap |
     // block records | sample coordinates (the point operands are built from them) | with a dynamic net: the
     // static net's per-sample results, parked while the dynamic net runs (registers the engine needs: the
@@ -528,8 +536,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
 #pragma unroll
                 for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
             };
-            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true>(tiles, unit, pts_copy, feat_s,
-                                                                   views_of(a.st, cams_s), head_s, rgb_s);
+            engine_forward<EP, CB, 4, MOD_S, NT_FEAT_S, V2S, true, PF, CONT>(tiles, unit, pts_copy, feat_s,
+                                                                             views_of(a.st, cams_s), head_s, rgb_s);
         }
         ZEST_STAMP(st_eng);
         // ---- per-block compositing on lanes 0 .. BS-1 (sample = lane): rgb rows 0-2, head rows 0, 1
@@ -582,8 +590,8 @@ __global__ __launch_bounds__(kFusedWaves * 64, kFusedWaves * ZEST_FUSED_WG_PER_C
 #pragma unroll
                     for (int cb = 0; cb < CB; cb++) o[cb] = pts_keep[cb];
                 };
-                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true>(tiles, unit, pts_copy, feat_d,
-                                                                         views_of(a.dy, cams_d), head_d, rgb_d);
+                engine_forward<EP, CB, 6, MOD_D, NT_FEAT_D, false, true, PF, CONT>(tiles, unit, pts_copy, feat_d,
+                                                                                   views_of(a.dy, cams_d), head_d, rgb_d);
             }
             ZEST_STAMP(st_eng);
             const float2 s0 = st_lds[(wave * 3 + 0) * 32 + cbs], s1 = st_lds[(wave * 3 + 1) * 32 + cbs],

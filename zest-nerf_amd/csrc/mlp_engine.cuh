@@ -283,16 +283,24 @@ __device__ __forceinline__ void engine_fp16_overflow_clamp() {
     __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1);        // hwreg(HW_REG_MODE, offset 23 = FP16_OVFL, 1 bit) = 1
 }
 
-#ifndef ZEST_PREFETCH
-#define ZEST_PREFETCH 3        // weight tiles kept in flight ahead of the MFMAs that consume them
+// Weight tiles kept in flight ahead of the MFMAs that consume them: the read-ahead depth PF of engine_layer, a template
+// argument per kernel family.  kPrefetch is what the kernels at 229-256 VGPRs can afford.  kPrefetchLone is for the
+// kernels with registers to spare (16-bit operands, no features; +12 VGPRs): when its SIMD partner waits at a
+// rendezvous or has no block, a wave has the matrix pipe to itself, and 3 tiles = 6 MFMAs (~96 cycles) of cover are
+// less than an LDS round trip with eight waves reading.  Depths 3 / 4 / 6 / 8 on the headline kernel (continuous
+// window, below): -1.0 / -0.9 / -1.8 / -1.3 % of the step (profiles/ring_protocol_parent_vs_child.txt).
+// -DZEST_PREFETCH=n (A/B builds) sets one depth for every kernel.
+#ifdef ZEST_PREFETCH
+constexpr int kPrefetch = ZEST_PREFETCH, kPrefetchLone = ZEST_PREFETCH;
+#else
+constexpr int kPrefetch = 3, kPrefetchLone = 6;
 #endif
-constexpr int kPrefetch = ZEST_PREFETCH;
 
 // What is fetched ahead for one row block: its bias initialisers and its first tiles.
-template <int NP>
+template <int NP, int PF>
 struct RowBlockPre {
     f32x4 bias[2], mbias[2];      // per row tile
-    bf16x8 win[kPrefetch][NP];
+    bf16x8 win[PF][NP];
 };
 
 // One Linear: NJB row blocks (32 outputs = row tiles 0, 1) over the operand
@@ -303,9 +311,17 @@ struct RowBlockPre {
 //         (head / rgb: lane group g holds rows 4g .. 4g+3)
 // Unit order inside a row block: header, then per k-tile the row tiles 0, 1 (modulation k-tiles
 // first; a split tile is the unit pair hi, lo): independent accumulators take turns.  The LDS
-// reads are software-pipelined by hand, in source order: every tile is requested kPrefetch tiles
-// before the MFMAs that use it, and the NEXT row block's header and first tiles are requested
-// before the CURRENT epilogue, whose VALU instructions cover their latency.
+// reads are software-pipelined by hand, in source order: every tile is requested P = min(PF, tiles of a row block)
+// tiles before the MFMAs that use it.
+//   CONT = false: the NEXT row block's header and first tiles are requested behind the current row block's last
+//         MFMA, before its epilogue, whose VALU instructions cover part of their latency.  The window runs empty at
+//         the end of every row block (the listing counts lgkmcnt down to 0 there).
+//   CONT = true: the window runs on across the row blocks of a layer: the next row block's header and first tiles
+//         are requested inside the current k loop, each P tiles ahead of its MFMAs as every other tile is.  With a
+//         partner on the matrix pipe the refill hides behind the partner's MFMAs; a wave alone on its SIMD waits an
+//         LDS round trip per row block without it.  Units are still requested in stream order, so every chunk is
+//         entered exactly once and in order; no value changes.  The split-fp16 feature kernels and the standalone
+//         / training kernels answer with scratch and keep CONT = false.
 // A sink sees every finished operand tile of the layers that have one (training: the activation stash):
 //   sink(id, jb, cb, v)   id: 0-7 trunk layers, 8 feature_linear, 9 view layer; v: the 8 fp32 values
 struct NoSink {
@@ -318,8 +334,8 @@ struct NoSink {
 // 2 880 MFMAs, on the port the engine is short of (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost') - and a
 // scalar branch per row block cuts the unrolled network into basic blocks the register allocator answers with
 // ~200 spills.
-template <int EP, int CB, int NJB, int NKA, int NKB, bool MOD, int NKF, bool RELU, int MODE, bool V2, class Tiles,
-          class Sink = NoSink>
+template <int EP, int CB, int NJB, int NKA, int NKB, bool MOD, int NKF, bool RELU, int MODE, bool V2, int PF, bool CONT,
+          class Tiles, class Sink = NoSink>
 __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
                                              const OpArr<NKA, ep_parts(EP)> (&opa)[CB],
                                              const OpArr<NKB, ep_parts(EP)> (&opb)[CB],
@@ -332,29 +348,33 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
     static_assert(T >= 1, "empty layer");
     // a sink wants the activated fp32 values: only the plain inference layer rounds first
     constexpr bool kPackedRelu = RELU && MODE == 0 && EP != ZEST_PREC_F16X3 && __is_same(Sink, NoSink);
-    auto preload = [&](RowBlockPre<NP> &p, int u0) {            // u0: the row block's header unit
+    constexpr int P = PF < T ? PF : T;                          // tiles in flight in this layer
+    auto preload_header = [&](RowBlockPre<NP, PF> &p, int u0) {   // u0: the row block's header unit
 #pragma unroll
         for (int rt = 0; rt < 2; rt++) {
             p.bias[rt] = tiles.load_bias(u0, 0, rt);
             if (MOD) p.mbias[rt] = tiles.load_bias(u0, 1, rt);
         }
-#pragma unroll
-        for (int k = 0; k < kPrefetch; k++)
-            if (k < T) {
-#pragma unroll
-                for (int pt = 0; pt < NP; pt++) p.win[k][pt] = tiles.load(u0 + 1 + NP * k + pt);
-            }
     };
-    RowBlockPre<NP> pre;
+    auto preload_tile = [&](RowBlockPre<NP, PF> &p, int u0, int k) {
+#pragma unroll
+        for (int pt = 0; pt < NP; pt++) p.win[k][pt] = tiles.load(u0 + 1 + NP * k + pt);
+    };
+    auto preload = [&](RowBlockPre<NP, PF> &p, int u0) {
+        preload_header(p, u0);
+#pragma unroll
+        for (int k = 0; k < P; k++) preload_tile(p, u0, k);
+    };
+    RowBlockPre<NP, PF> pre;
     preload(pre, unit);
 #pragma unroll
     for (int jb = 0; jb < NJB; jb++) {
         const int u0 = unit;
         // acc: the hi*hi products (all products of the one-part types); corr: hi*lo + lo*hi, scaled 2^11
         f32x4 acc[2][CB], macc[2][CB], corr[2][CB], mcorr[2][CB];
-        bf16x8 win[kPrefetch][NP];
+        bf16x8 win[P][NP];
 #pragma unroll
-        for (int k = 0; k < kPrefetch; k++)
+        for (int k = 0; k < P; k++)
 #pragma unroll
             for (int pt = 0; pt < NP; pt++) win[k][pt] = pre.win[k][pt];
 #pragma unroll
@@ -369,7 +389,7 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
         for (int k = 0; k < T; k++) {
             bf16x8 a[NP];
 #pragma unroll
-            for (int pt = 0; pt < NP; pt++) a[pt] = win[k % kPrefetch][pt];
+            for (int pt = 0; pt < NP; pt++) a[pt] = win[k % P][pt];
             const int rt = k % 2, kt = (k < NM ? k : k - NM) / 2;          // compile-time after unrolling
 #pragma unroll
             for (int cb = 0; cb < CB; cb++) {
@@ -394,13 +414,16 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
                     }
                 }
             }
-            if (k + kPrefetch < T) {
+            if (k + P < T) {
 #pragma unroll
-                for (int pt = 0; pt < NP; pt++) win[k % kPrefetch][pt] = tiles.load(u0 + 1 + NP * (k + kPrefetch) + pt);
+                for (int pt = 0; pt < NP; pt++) win[k % P][pt] = tiles.load(u0 + 1 + NP * (k + P) + pt);
+            } else if (CONT && jb + 1 < NJB) {                  // tile k + P - T of the next row block
+                if (k + P == T) preload_header(pre, u0 + 1 + NP * T);
+                preload_tile(pre, u0 + 1 + NP * T, k + P - T);
             }
         }
         unit = u0 + 1 + NP * T;
-        if (jb + 1 < NJB) preload(pre, unit);                   // in flight during the epilogue
+        if (!CONT && jb + 1 < NJB) preload(pre, unit);          // in flight during the epilogue
 #pragma unroll
         for (int cb = 0; cb < CB; cb++) {
             float v[8];
@@ -444,11 +467,12 @@ __device__ __forceinline__ void engine_layer(const Tiles &tiles, int &unit,
 // `views_fn(views)` builds the direction operand when it is first needed (op 10).
 // Results per column block: head (lane group g: rows 4g .. 4g+3 of the head
 // tile; row 0 alpha, rows 1.. extra heads) and rgb (group 0: rows 0-2), raw.
+// PF, CONT: read-ahead depth and window shape of every layer (engine_layer), chosen per kernel family.
 // FOLD: the stream is the inference stream (mlp_plan.h): no feature_linear layer (sink id 8 is never seen), the
 // view layer multiplies the trunk output itself.  The training forward, whose backward needs the feature_linear
 // output in the stash, runs FOLD = false on the plain stream.
-template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool FOLD = false, class Tiles,
-          class PtsFn, class ViewsFn, class Sink = NoSink>
+template <int EP, int CB, int NU_PTS, bool MOD, int NU_FEAT, bool V2, bool FOLD = false, int PF = kPrefetch,
+          bool CONT = false, class Tiles, class PtsFn, class ViewsFn, class Sink = NoSink>
 __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, PtsFn pts_fn,
                                                const OpArr<NU_FEAT / 2, ep_parts(EP)> (&feat)[CB], ViewsFn views_fn,
                                                f32x4 (&head)[CB], f32x4 (&rgb)[CB], const Sink &sink = Sink()) {
@@ -461,28 +485,28 @@ __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, Pt
     {
         OpArr<KP, NP> pts[CB];
         pts_fn(pts);
-        engine_layer<EP, CB, 8, KP, 0, MOD, KF, true, 0, V2>(tiles, unit, pts, none, feat, hA, unused, 0, sink);
+        engine_layer<EP, CB, 8, KP, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, pts, none, feat, hA, unused, 0, sink);
     }
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 1, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 2, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 3, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 4, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hA, none, feat, hB, unused, 1, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hB, none, feat, hA, unused, 2, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hA, none, feat, hB, unused, 3, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hB, none, feat, hA, unused, 4, sink);
     {
         OpArr<KP, NP> pts[CB];
         pts_fn(pts);
-        engine_layer<EP, CB, 8, KP, 8, MOD, KF, true, 0, V2>(tiles, unit, pts, hA, feat, hB, unused, 5, sink);
+        engine_layer<EP, CB, 8, KP, 8, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, pts, hA, feat, hB, unused, 5, sink);
     }
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 6, sink);
-    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2>(tiles, unit, hA, none, feat, hB, unused, 7, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hB, none, feat, hA, unused, 6, sink);
+    engine_layer<EP, CB, 8, 8, 0, MOD, KF, true, 0, V2, PF, CONT>(tiles, unit, hA, none, feat, hB, unused, 7, sink);
     // trunk output in hB
-    engine_layer<EP, CB, 1, 8, 0, false, KF, false, 1, V2>(tiles, unit, hB, none, feat, hA, head);
+    engine_layer<EP, CB, 1, 8, 0, false, KF, false, 1, V2, PF, CONT>(tiles, unit, hB, none, feat, hA, head);
     if constexpr (!FOLD)
-        engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
+        engine_layer<EP, CB, 8, 8, 0, false, KF, false, 0, V2, PF, CONT>(tiles, unit, hB, none, feat, hA, unused, 8, sink);
     // view layer: on the feature_linear output (hA -> hB), or folded on the trunk output itself (hB -> hA)
     OpArr<8, NP> (&vin)[CB] = FOLD ? hB : hA, (&vout)[CB] = FOLD ? hA : hB;
     OpArr<1, NP> views[CB];
     views_fn(views);
-    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2>(tiles, unit, vin, views, feat, vout, unused, 9, sink);
+    engine_layer<EP, CB, 4, 8, 1, false, KF, true, 0, V2, PF, CONT>(tiles, unit, vin, views, feat, vout, unused, 9, sink);
     // rgb: 128 hidden features = first 4 k-tiles of the view layer's output
     OpArr<4, NP> h128[CB];
 #pragma unroll
@@ -491,7 +515,7 @@ __device__ __forceinline__ void engine_forward(const Tiles &tiles, int &unit, Pt
         for (int pt = 0; pt < NP; pt++)
 #pragma unroll
             for (int k = 0; k < 4; k++) h128[cb].t[pt][k] = vout[cb].t[pt][k];
-    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2>(tiles, unit, h128, none, feat, vin, rgb);
+    engine_layer<EP, CB, 1, 4, 0, false, KF, false, 1, V2, PF, CONT>(tiles, unit, h128, none, feat, vin, rgb);
     tiles.finish(unit, unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD));
     unit = unit0 + stream_units(NU_PTS, MOD ? NU_FEAT : 0, NP, FOLD);
 }

@@ -674,14 +674,48 @@ int zest_volume_from_cl(const float *vol_cl, int D, int H, int W, float *vol, vo
  * ZEST_P_* slot, same layout as zest_mlp_pack; g_params entries are overwritten).
  * saved / workspace: caller-owned scratch of zest_mlp_train_saved_floats /
  * zest_mlp_train_workspace_floats floats; `saved` and `out` of the forward call must be handed
- * unchanged to the backward call.  GEMMs run in rocBLAS sgemm (plain library shapes). */
+ * unchanged to the backward call.
+ *
+ * The GEMMs of this path come in two kinds, chosen per call by the trailing `gemm` of the _ex entries:
+ *   ZEST_GEMM_LIBRARY     rocBLAS sgemm (plain library shapes); what the entries without _ex run.
+ *   ZEST_GEMM_SPLIT_BF16  the project's own kernels (csrc/train_gemm.hip): every fp32 operand value is split into
+ *                         three bf16 terms (fp32's exponent range) and a product is six bf16 MFMAs into one fp32
+ *                         accumulator - sgemm's error class (<= 2^-22 relative to sum |a||b| from the dropped
+ *                         terms), no library call: only kernel launches and device-to-device copies on the stream
+ *                         (capturable in a HIP graph by construction; not covered by a test).  With it the
+ *                         weight and data gradients are bit-reproducible from run to run (fixed summation order,
+ *                         no atomics); the BIAS gradients still are not: their column sums use float atomics in
+ *                         either mode.  Non-finite inputs give non-finite outputs (inf - inf in the split), not
+ *                         necessarily the library's kind of non-finite.
+ * The workspace of the _ex calls is zest_mlp_train_workspace_floats_ex floats (never less than the plain query). */
+enum { ZEST_GEMM_LIBRARY = 0, ZEST_GEMM_SPLIT_BF16 = 1 };
+enum { ZEST_GEMM_OP_NT = 0, ZEST_GEMM_OP_NN = 1, ZEST_GEMM_OP_TN = 2 };
 size_t zest_mlp_train_saved_floats(const zest_mlp_desc *desc, int M);
 size_t zest_mlp_train_workspace_floats(const zest_mlp_desc *desc, int M);
+size_t zest_mlp_train_workspace_floats_ex(const zest_mlp_desc *desc, int M, int gemm);
 int zest_mlp_train_fwd(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
                        float *saved, float *workspace, float *out, void *stream);
 int zest_mlp_train_bwd(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
                        const float *saved, const float *out, const float *g_out, float *workspace,
                        float *g_x, float *const *g_params, void *stream);
+int zest_mlp_train_fwd_ex(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
+                          float *saved, float *workspace, float *out, void *stream, int gemm);
+int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
+                          const float *saved, const float *out, const float *g_out, float *workspace,
+                          float *g_x, float *const *g_params, void *stream, int gemm);
+
+/* One GEMM of that path, fp32 row-major operands with leading dimensions, through either kind (`gemm`):
+ *   ZEST_GEMM_OP_NT  c[M,N] (ldc) = a[M,K] (lda) . b[N,K]^T (ldb) + beta c       (a = X, b = Wt, c = Y)
+ *   ZEST_GEMM_OP_NN  c[M,K] (ldc) = a[M,N] (lda) . b[N,K]   (ldb) + beta c       (a = dY, b = Wt, c = dX)
+ *   ZEST_GEMM_OP_TN  c[N,K] (ldc) = a[M,N]^T (lda) . b[M,K] (ldb)                (a = dY, b = X, c = dWt; beta = 0)
+ * M >= 0 (0: no-op), 1 <= N, K <= 256, beta 0 or 1, every leading dimension at least its row.  Only c[.., :row] is
+ * written.  workspace: zest_train_gemm_workspace_floats floats (the TN partials; for NT and NN the split kernels'
+ * packed weight planes - the library path needs none there and takes NULL).  TN contracts M in
+ * chunks of zest_train_gemm_chunk_rows rows whose partial products are summed in chunk order. */
+size_t zest_train_gemm_workspace_floats(int op, int M, int N, int K);
+int zest_train_gemm_chunk_rows(void);
+int zest_train_gemm(int gemm, int op, int M, int N, int K, const float *a, int lda, const float *b, int ldb,
+                    float *c, int ldc, float beta, float *workspace, void *stream);
 
 /* ---- MLP training path, bf16 operands on the MFMA engine (hand-written forward AND backward) ----
  * The fast training mode ('v0' nets).  Forward: the inference engine kernel, which additionally

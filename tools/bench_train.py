@@ -30,10 +30,13 @@ def main():
     ap.add_argument("--cpu-rays", type=int, default=64)
     ap.add_argument("--precision", type=int, default=16, choices=[16, 32],
                     help="16: bf16 MFMA training kernels (MlpFn16); 32: fp32 parity path (rocBLAS sgemm)")
+    ap.add_argument("--gemm", default="library", choices=["library", "split"],
+                    help="GEMMs of the fp32 path: rocBLAS sgemm, or the three-term bf16 MFMA kernels (ignored with --precision 16)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     d = bench.build_workload("nsff_zest_val_1024x128", 5, dev, a.rays)
-    d.args.precision, d.args.zest_maps_only = a.precision, False
+    d.args.precision, d.args.zest_maps_only, d.args.zest_train_gemm = a.precision, False, a.gemm
+    mlp_name = "bf16 MFMA" if a.precision == 16 else "fp32 rocBLAS" if a.gemm == "library" else "fp32-class split-bf16 MFMA"
     vol_s, vol_d = d.vol_s.clone().requires_grad_(True), d.vol_d.clone().requires_grad_(True)
     params = list(d.net_s.parameters()) + list(d.net_d.parameters())
 
@@ -61,7 +64,7 @@ def main():
         step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    out = {"op": "train step (rendering fwd + bwd, %d-frame ZeST, %s MLP)" % (a.frames, "bf16 MFMA" if a.precision == 16 else "fp32 rocBLAS"), "rays": d.R, "samples": d.S,
+    out = {"op": "train step (rendering fwd + bwd, %d-frame ZeST, %s MLP)" % (a.frames, mlp_name), "rays": d.R, "samples": d.S,
            "ms_per_step": dt * 1e3, "rays_per_s": d.R / dt,
            "peak_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}
     if a.cpu_rays <= 0:

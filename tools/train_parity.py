@@ -3,7 +3,8 @@
 (lr 5e-4, the reference's --lrate, opt.py:58) for N steps by
 
   oracle   the CPU oracle (reference op sequence, oracle/zest_oracle.py) under torch autograd, fp32
-  hip32    renderer.rendering(..., val=False) under autograd, --precision 32 (HIP kernels + rocBLAS sgemm)
+  hip32    renderer.rendering(..., val=False) under autograd, --precision 32 (HIP kernels + rocBLAS sgemm; with ZEST_TRAIN_GEMM=split
+           in the environment the GEMMs run on the three-term bf16 MFMA kernels instead)
   hip16    the same call with --precision 16: both MLPs forward and backward on the bf16 MFMA kernels
 
 on a loss shaped like the reference's training step (train.py:346-585: colour terms on the blended, the static and

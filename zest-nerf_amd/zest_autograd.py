@@ -104,13 +104,14 @@ def _slot_grads(slots, grads):
 
 class MlpFn(Function):
     @staticmethod
-    def forward(ctx, x, desc, slots, *params):
-        """params: the (weight, bias) tensors of the slots in `slots` (ZEST_P_* order)."""
+    def forward(ctx, x, desc, slots, gemm, *params):
+        """params: the (weight, bias) tensors of the slots in `slots` (ZEST_P_* order).  gemm: zest_hip.GEMM_*, the
+        kind of GEMM forward and backward run on."""
         table = _param_table(slots, params)
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
-        out, saved = zest_hip.mlp_train_fwd(desc, table, x2)
-        ctx.desc, ctx.slots, ctx.lead = desc, slots, lead
+        out, saved = zest_hip.mlp_train_fwd(desc, table, x2, gemm=gemm)
+        ctx.desc, ctx.slots, ctx.lead, ctx.gemm = desc, slots, lead, gemm
         ctx.save_for_backward(x2, saved, out, *params)
         return out.view(*lead, desc.out_ch)
 
@@ -120,8 +121,9 @@ class MlpFn(Function):
         table = _param_table(ctx.slots, params)
         g_x, grads = zest_hip.mlp_train_bwd(ctx.desc, table, x2, saved, out,
                                             g_out.reshape(-1, ctx.desc.out_ch).contiguous(),
-                                            want_gx=ctx.needs_input_grad[0])
-        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, *_slot_grads(ctx.slots, grads))
+                                            want_gx=ctx.needs_input_grad[0], gemm=ctx.gemm)
+        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, None,
+                *_slot_grads(ctx.slots, grads))
 
 
 class MlpFn16(Function):
@@ -249,11 +251,13 @@ def split_last(raw, sizes):
     return raw.split(sizes, -1)
 
 
-def mlp_apply(net, x, time_codes=None, bf16=False, shared=None):
+def mlp_apply(net, x, time_codes=None, bf16=False, shared=None, gemm=zest_hip.GEMM_LIBRARY):
     """Training forward of a zest networks.MVSNeRF on x [..., C_in] with autograd.  time_codes: the
     frame's latent code for a net with time-code channels (folded into layer 0 / 5 biases with
     differentiable torch ops: gradients reach the code and the full-width weights).  bf16: the fast
-    training mode (MlpFn16, 'v0' nets); otherwise the fp32 parity path (MlpFn).  shared: see MlpFn16."""
+    training mode (MlpFn16, 'v0' nets); otherwise the fp32 parity path (MlpFn), whose GEMMs run on
+    `gemm` (zest_hip.GEMM_LIBRARY: rocBLAS sgemm; GEMM_SPLIT_BF16: the three-term bf16 MFMA kernels).  shared: see
+    MlpFn16."""
     mod = net.nerf
     desc = mod._desc()
     named = mod.effective_parameters(time_codes)
@@ -273,7 +277,7 @@ def mlp_apply(net, x, time_codes=None, bf16=False, shared=None):
         warnings.warn("zest: --precision 16 training of a %s net takes the fp32 training path (rocBLAS sgemm): the "
                       "bf16 MFMA training kernels cover 'v0' nets of depth 8 / width 256 / skips [4]"
                       % ("'v2'" if desc.net_type else "D=%d W=%d" % (desc.D, desc.W)), stacklevel=2)
-    return MlpFn.apply(x, desc, tuple(slots), *params)
+    return MlpFn.apply(x, desc, tuple(slots), gemm, *params)
 
 
 class VolumeCostFn(Function):

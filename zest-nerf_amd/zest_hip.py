@@ -21,6 +21,9 @@ PREC_F32, PREC_BF16, PREC_F16, PREC_F16X3 = 0, 1, 2, 3
 ENGINE_PRECISIONS = (PREC_BF16, PREC_F16, PREC_F16X3)
 PREC_NAMES = {PREC_F32: "f32", PREC_BF16: "bf16", PREC_F16: "f16", PREC_F16X3: "f16x3"}
 HEAD_NONE, HEAD_BLEND, HEAD_DYNAMIC = 0, 1, 2
+GEMM_LIBRARY, GEMM_SPLIT_BF16 = 0, 1          # ZEST_GEMM_*: the GEMMs of the fp32 training path
+GEMM_NAMES = {"library": GEMM_LIBRARY, "split": GEMM_SPLIT_BF16}
+GEMM_OP_NT, GEMM_OP_NN, GEMM_OP_TN = 0, 1, 2
 P_COUNT = 15
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -147,6 +150,13 @@ _SIGS = {
     "zest_mlp_train_fwd": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp]),
     "zest_mlp_train_bwd": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                 C.POINTER(_vp), _vp]),
+    "zest_mlp_train_workspace_floats_ex": (_sz, [C.POINTER(MlpDesc), _i, _i]),
+    "zest_mlp_train_fwd_ex": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _i]),
+    "zest_mlp_train_bwd_ex": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(_vp), _vp, _i]),
+    "zest_train_gemm_workspace_floats": (_sz, [_i, _i, _i, _i]),
+    "zest_train_gemm_chunk_rows": (_i, []),
+    "zest_train_gemm": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp]),
     "zest_mlp_train16_stash_bytes": (_sz, [C.POINTER(MlpDesc), _i]),
     "zest_mlp_train16_work_bytes": (_sz, [C.POINTER(MlpDesc), _i]),
     "zest_mlp_train16_packed_bytes": (_sz, [C.POINTER(MlpDesc)]),
@@ -1503,34 +1513,99 @@ def _mlp_rows(desc, x, name="x"):
     return x
 
 
-def mlp_train_fwd(desc, params, x):
-    """params: 2*P_COUNT tensors-or-None.  -> out [M,C_out], saved (opaque activation stash)."""
+def _gemm_kind(gemm):
+    if gemm not in (GEMM_LIBRARY, GEMM_SPLIT_BF16):
+        raise RuntimeError("zest_hip: gemm must be GEMM_LIBRARY (0) or GEMM_SPLIT_BF16 (1), got %r" % (gemm,))
+    return int(gemm)
+
+
+def _gemm_operand(t, name, rows=None, cols=None):
+    """A 2-D fp32 device matrix whose rows are contiguous; the row stride is its leading dimension (views into
+    wider buffers are taken as they are: that is how the training path writes sub-blocks in place)."""
+    if not t.is_cuda:
+        raise RuntimeError("zest_hip: %s is on %s; this path runs only on a HIP device" % (name, t.device))
+    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError("zest_hip: %s must be a 2-D fp32 matrix with contiguous rows" % name)
+    if (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+        raise RuntimeError("zest_hip: %s has shape %s, expected (%s, %s)" % (name, tuple(t.shape), rows, cols))
+    if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+        raise RuntimeError("zest_hip: rows of %s overlap" % name)
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1])))
+
+
+def train_gemm_chunk_rows():
+    """Rows of M per partial product of the TN operation."""
+    return int(lib().zest_train_gemm_chunk_rows())
+
+
+def train_gemm(gemm, op, a, b, c=None, beta=0.0):
+    """One GEMM of the fp32 training path through the library (GEMM_LIBRARY) or the split-bf16 kernels
+    (GEMM_SPLIT_BF16).  GEMM_OP_NT: c[M,N] = a[M,K] b[N,K]^T + beta c;  GEMM_OP_NN: c[M,K] = a[M,N] b[N,K] + beta c;
+    GEMM_OP_TN: c[N,K] = a[M,N]^T b[M,K].  Operands are 2-D fp32 matrices with contiguous rows, views with a larger
+    row stride included; c is written in place (only its [rows, cols] block) and returned."""
+    gemm = _gemm_kind(gemm)
+    if op not in (GEMM_OP_NT, GEMM_OP_NN, GEMM_OP_TN):
+        raise RuntimeError("zest_hip: op must be GEMM_OP_NT, GEMM_OP_NN or GEMM_OP_TN, got %r" % (op,))
+    a, lda = _gemm_operand(a, "a")
+    M = a.shape[0]
+    if op == GEMM_OP_NT:
+        K = a.shape[1]
+        b, ldb = _gemm_operand(b, "b", None, K)
+        N = b.shape[0]
+        c_shape = (M, N)
+    elif op == GEMM_OP_NN:
+        N = a.shape[1]
+        b, ldb = _gemm_operand(b, "b", N, None)
+        K = b.shape[1]
+        c_shape = (M, K)
+    else:
+        N = a.shape[1]
+        b, ldb = _gemm_operand(b, "b", M, None)
+        K = b.shape[1]
+        c_shape = (N, K)
+    if c is None:
+        if beta != 0.0:
+            raise RuntimeError("zest_hip: train_gemm with beta != 0 needs c")
+        c = torch.empty(c_shape, device=a.device, dtype=torch.float32)
+    c, ldc = _gemm_operand(c, "c", *c_shape)
+    L = lib()
+    work = torch.empty(int(L.zest_train_gemm_workspace_floats(op, M, N, K)), device=a.device)
+    _check(L.zest_train_gemm(gemm, op, M, N, K, _ptr(a), lda, _ptr(b), ldb, _ptr(c), ldc, float(beta),
+                             _ptr(work) if work.numel() else None, _stream(a)), "zest_train_gemm")
+    return c
+
+
+def mlp_train_fwd(desc, params, x, gemm=GEMM_LIBRARY):
+    """params: 2*P_COUNT tensors-or-None.  -> out [M,C_out], saved (opaque activation stash).
+    gemm: GEMM_LIBRARY (rocBLAS sgemm) or GEMM_SPLIT_BF16 (three-term bf16 MFMA kernels)."""
+    gemm = _gemm_kind(gemm)
     x = _mlp_rows(desc, x)
     M = x.numel() // x.shape[-1]
     L = lib()
     saved = torch.empty(int(L.zest_mlp_train_saved_floats(C.byref(desc), M)), device=x.device)
-    work = torch.empty(int(L.zest_mlp_train_workspace_floats(C.byref(desc), M)), device=x.device)
+    work = torch.empty(int(L.zest_mlp_train_workspace_floats_ex(C.byref(desc), M, gemm)), device=x.device)
     out = torch.empty(*x.shape[:-1], desc.out_ch, device=x.device, dtype=torch.float32)
     keep = _params(desc, params)
-    _check(L.zest_mlp_train_fwd(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(work), _ptr(out),
-                                _stream(x)), "zest_mlp_train_fwd")
+    _check(L.zest_mlp_train_fwd_ex(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(work), _ptr(out),
+                                   _stream(x), gemm), "zest_mlp_train_fwd")
     return out, saved
 
 
-def mlp_train_bwd(desc, params, x, saved, out, g_out, want_gx=True):
+def mlp_train_bwd(desc, params, x, saved, out, g_out, want_gx=True, gemm=GEMM_LIBRARY):
     """-> g_x [.., C_in] or None, list of 2*P_COUNT parameter gradients (None where absent)."""
+    gemm = _gemm_kind(gemm)
     x = _mlp_rows(desc, x)
     M = x.numel() // x.shape[-1]
     g_out, out = _dev(g_out, "g_out", x.shape[:-1] + (desc.out_ch,)), _dev(out, "out", x.shape[:-1] + (desc.out_ch,))
     L = lib()
     if saved.numel() < int(L.zest_mlp_train_saved_floats(C.byref(desc), M)):
         raise RuntimeError("zest_hip: `saved` is not the stash of this forward call (too small)")
-    work = torch.empty(int(L.zest_mlp_train_workspace_floats(C.byref(desc), M)), device=x.device)
+    work = torch.empty(int(L.zest_mlp_train_workspace_floats_ex(C.byref(desc), M, gemm)), device=x.device)
     keep = _params(desc, params)
     grads = [(torch.empty_like(p) if p is not None else None) for p in keep]
     g_x = torch.empty_like(x) if want_gx else None
-    _check(L.zest_mlp_train_bwd(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(out), _ptr(g_out),
-                                _ptr(work), _ptr(g_x), _ptr_table(grads), _stream(x)), "zest_mlp_train_bwd")
+    _check(L.zest_mlp_train_bwd_ex(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(out), _ptr(g_out),
+                                   _ptr(work), _ptr(g_x), _ptr_table(grads), _stream(x), gemm), "zest_mlp_train_bwd")
     return g_x, grads
 
 

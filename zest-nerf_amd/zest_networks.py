@@ -23,7 +23,7 @@ import torch.nn as nn
 
 import zest_hip
 
-__all__ = ["Embedding", "Renderer", "Renderer_linear", "MVSNeRF", "resolve_precision", "inference_precision",
+__all__ = ["Embedding", "Renderer", "Renderer_linear", "MVSNeRF", "resolve_precision", "inference_precision", "train_gemm_choice",
            "ActivatedBatchNorm", "ConvBnReLU", "ConvBnReLU3D", "FeatureNet", "CostRegNet", "MVSNet",
            "MVSNeRF_G", "DyMVSNeRF_G", "GRAFDiscriminator"]
 
@@ -48,6 +48,29 @@ def resolve_precision(args=None):
             raise ValueError("args.zest_dtype16=%r: expected 'bf16' or 'f16'" % (name,))
         return _PREC_BY_NAME[name]
     return zest_hip.PREC_F32
+
+
+_warned_train_gemm16 = False
+
+
+def train_gemm_choice(args=None, train16=False):
+    """-> zest_hip.GEMM_*: the GEMMs of the fp32 training path, from args.zest_train_gemm, else the environment
+    variable ZEST_TRAIN_GEMM, else "library" (rocBLAS sgemm); "split" selects the three-term bf16 MFMA kernels
+    (fp32-class results, no library call).  --precision 16 trains on the bf16 kernels and has no such GEMMs: the
+    choice is then ignored, with one warning per process."""
+    global _warned_train_gemm16
+    name = getattr(args, "zest_train_gemm", None) or os.environ.get("ZEST_TRAIN_GEMM") or "library"
+    if name not in zest_hip.GEMM_NAMES:
+        raise ValueError("zest: zest_train_gemm / ZEST_TRAIN_GEMM must be one of %s, got %r"
+                         % (sorted(zest_hip.GEMM_NAMES), name))
+    if train16 and name != "library":
+        if not _warned_train_gemm16:
+            import warnings
+            warnings.warn("zest: zest_train_gemm=%r is ignored in --precision 16 (it chooses the GEMMs of the fp32 "
+                          "training path)" % name, stacklevel=2)
+            _warned_train_gemm16 = True
+        return zest_hip.GEMM_LIBRARY
+    return zest_hip.GEMM_NAMES[name]
 
 
 def inference_precision(prec, args=None):
@@ -339,7 +362,7 @@ class MVSNeRF(nn.Module):
         if self.nerf.in_ch_time == 0 and torch.is_grad_enabled() and (
                 x.requires_grad or any(p.requires_grad for p in self.parameters())):
             import zest_autograd
-            return zest_autograd.mlp_apply(self, x)          # fp32 training path (HIP fwd + bwd)
+            return zest_autograd.mlp_apply(self, x, gemm=train_gemm_choice())     # fp32 training path (HIP fwd + bwd)
         return self.nerf(x)
 
 

@@ -20,7 +20,7 @@ Two execution plans:
 import torch
 
 import zest_hip
-from zest_networks import MVSNeRF, inference_precision, resolve_precision
+from zest_networks import MVSNeRF, inference_precision, resolve_precision, train_gemm_choice
 from zest_utils import images_channels_last, volume_channels_last
 
 __all__ = ["rendering", "render_hierarchical", "raw2outputs", "raw2outputs_blending", "raw2alpha", "depth2dist",
@@ -241,11 +241,13 @@ def rendering(args, rays_pts, rays_ndc, depth_candidates, rays_dir,
                       "trains on the bf16 MFMA kernels (a gradient wants bf16's exponent range), so this run trains in "
                       "bf16 and evaluates in fp16", stacklevel=2)
 
+    gemm = train_gemm_choice(args, train16) if train else zest_hip.GEMM_LIBRARY       # read once per call
+
     shared = {}                 # per net: what its passes of this call share (packed weight streams, work buffer)
 
     def mlp(net, x, tc=None):
         if train:
-            return za.mlp_apply(net, x, tc, bf16=train16, shared=shared.setdefault(id(net), {}))
+            return za.mlp_apply(net, x, tc, bf16=train16, shared=shared.setdefault(id(net), {}), gemm=gemm)
         p = net.nerf.engine_precision(mlp_prec)
         return zest_hip.mlp_fwd(net.desc(), p, net.packed(p, tc), x)
 

@@ -560,9 +560,39 @@ int zest_image_metrics(const float *pred, const long long *pred_stride, const fl
  * No float atomics: two calls on equal inputs are bit-identical.  n_launches == 0 does nothing.
  * Errors: NULL tables, bounds, grads or scalars; bounds that do not start at 0; a launch without tensors
  * or chunks or with more tensors than fit; a NULL gradient; with the clip on, NULL work or norm_out,
- * work_bytes too small, max_norm negative or not finite. */
+ * work_bytes too small, max_norm negative or not finite.
+ *
+ * zest_adam_step_amp: the same step under a GradScaler's protocol, decided on the device: no host read.
+ *   tensors .. launch_chunk, grads, clip, max_norm, work, work_bytes, norm_out, stream: as zest_adam_step.
+ *   launch_slots: HOST [n_launches]: rows of scalars launch l uses, 1..zest_adam_max_slots().
+ *   raw_scalars: HOST doubles [n_launches][zest_adam_max_slots()][ZEST_ADAM_RAW_SCALARS]: 0 lr, 1 b1, 2 b2,
+ *   3 eps, 4 1 - b1, 5 1 - b2, 6 t_host, the caller's count of ATTEMPTED steps including this one (a whole
+ *   number >= 1).  The kernel takes t = t_host - skipped and computes step_size = lr / (1 - b1^t) and
+ *   rbc2 = 1 / sqrt(1 - b2^t) in double, one thread per row, once per workgroup, rounds them to fp32 and
+ *   then runs the arithmetic above unchanged.
+ *   grad_scale: DEVICE, one fp32 value, or NULL.  Gradients are applied as g inv, inv = (float)(1 / (double)
+ *   scale) as torch's unscale_ computes it.  The sums of squares are those of the raw gradients; the norm
+ *   is inv sqrt(total) in double, that of the unscaled gradients, which is what the clip compares with
+ *   max_norm and what norm_out receives.  inv and the clip coefficient are ONE multiplier, their product in
+ *   double rounded to fp32 (inv itself where the coefficient is 1).
+ *   found_inf: DEVICE, one fp32 value, or NULL.  Non-zero (torch passes a sum over devices; a NaN counts)
+ *   skips the step.  skip_nonfinite != 0: the step is also skipped when the unscaled norm is inf or NaN;
+ *   the first launch then runs also with clip == 0 (coefficient 1), so work and norm_out are needed.  A
+ *   squared gradient element beyond fp32's range makes the norm inf and so skips.
+ *   A skipped step stores nothing to p, exp_avg, exp_avg_sq - no store instruction runs - but still writes
+ *   norm_out.  Every workgroup of every launch reads the same scale, found_inf, sums and counter, so all
+ *   decide alike.
+ *   skipped: DEVICE int32 [2], owned by the table, zero at first; parity: 0 or 1, flipped by the caller
+ *   after every call.  The call of parity k reads skipped[k] in every workgroup of every launch; thread 0
+ *   of workgroup 0 of the FIRST update launch alone writes skipped[k ^ 1] = skipped[k] + (skipped ? 1 : 0),
+ *   with a plain store: no atomics, and nothing in a call reads what that call writes, however many
+ *   launches it is cut into.  After the call, skipped[k ^ 1] counts the skipped steps of the table.
+ * Errors, beside those above: NULL raw_scalars, launch_slots or skipped; a parity other than 0 or 1;
+ * a row count outside 1..zest_adam_max_slots(); t_host < 1 or not whole in a row in use; skip_nonfinite
+ * with a NULL work or norm_out or work_bytes too small. */
 #define ZEST_ADAM_TENSOR_COLS 5
 #define ZEST_ADAM_SCALARS 6
+#define ZEST_ADAM_RAW_SCALARS 7
 int zest_adam_chunk(void);
 int zest_adam_max_tensors(void);
 int zest_adam_max_slots(void);
@@ -573,6 +603,11 @@ int zest_adam_step(const long long *tensors, const int *chunk_tensor, const long
                    const int *launch_tensor, const long long *launch_chunk, const void *const *grads,
                    const float *scalars, int clip, float max_norm, void *work, size_t work_bytes,
                    float *norm_out, void *stream);
+int zest_adam_step_amp(const long long *tensors, const int *chunk_tensor, const long long *chunk_offset,
+                       int n_launches, const int *launch_tensor, const long long *launch_chunk,
+                       const int *launch_slots, const void *const *grads, const double *raw_scalars, int clip,
+                       float max_norm, void *work, size_t work_bytes, float *norm_out, const float *grad_scale,
+                       const float *found_inf, int skip_nonfinite, int *skipped, int parity, void *stream);
 
 /* Trilinear lookup, zero padding, align_corners: index_point_feature
  * (reference utils.py:433-459).  vol_cl [H,W,D,8]; ndc [M,3] -> out [M,8]. */

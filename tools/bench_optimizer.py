@@ -16,7 +16,23 @@ composition is stated only where it exceeds the spread of its two measurements; 
 clip_grad_norm_ scales the gradients in place, so torch's gradients shrink to norm 1 in the first call and are multiplied
 by 1 from then on: the work per call does not change.
 
+The --amp leg times the same update as Trainer(precision=16) runs it, under a real torch.amp.GradScaler("cuda"), on the
+generator's parameters with gradients pre-multiplied by the scale; per iteration, on the host clock: scaler.unscale_(opt)
+where the variant needs it, the clip, scaler.step(opt), scaler.update():
+
+  generic      zest_optim.Adam(max_grad_norm=1) as a GradScaler treats any optimiser: unscale_, then its generic path,
+               which reads found_inf on the host before it calls step(); measured twice (.., generic_again) for the spread
+  fused        torch.optim.Adam(fused=True): unscale_, clip_grad_norm_, scaler.step (torch's fused Adam takes the scaler's
+               tensors itself)
+  amp          zest_optim.Adam(max_grad_norm=1, amp_scaling=True): scaler.step alone; the kernel unscales, clips and skips
+
+Here the device is synchronised only at the END of each block, so that the host runs ahead as it does in training and a
+synchronise hidden in a step shows as lost overlap.  unscale_ divides the gradients in place, so those of the first two
+variants shrink towards zero over the run; the kernels and their work do not change.  The scale is held (growth_interval
+beyond the run).  The claim is whether generic - amp exceeds the spread of generic's two measurements.
+
     python tools/bench_optimizer.py [--iters 400] [--out profiles/optimizer_step.json]
+    python tools/bench_optimizer.py --amp [--iters 400] [--out profiles/optimizer_step_amp.json]
     python tools/bench_optimizer.py --loop 200       # only zest_optim.Adam with the clip, for a kernel-trace profiler run
 """
 import argparse
@@ -36,6 +52,8 @@ DEV = "cuda:0"
 LR = 5e-4
 OURS = ("adam_sumsq_kernel", "adam_update_kernel")
 WAYS = ("torch", "fused", "hip", "torch_again")
+AMP_WAYS = ("generic", "fused", "amp", "generic_again")
+AMP_SCALE = 2.0 ** 10
 
 
 def parameter_sets():
@@ -70,12 +88,67 @@ def build(way, clip, groups, seed):
     return step, opt
 
 
+def build_amp(way, groups, seed):
+    """-> one iteration of `way` under its own GradScaler, as a callable."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    params = [[torch.nn.Parameter((0.1 * torch.randn(s, generator=g)).to(DEV)) for s in shapes] for shapes in groups]
+    for ps in params:
+        for p in ps:
+            p.grad = (torch.randn(p.shape, generator=g) * 1e-2 * AMP_SCALE).to(DEV)
+    spec = [{"params": params[0]}] + ([{"params": params[1], "lr": LR * 10}] if params[1] else [])
+    flat = params[0] + params[1]
+    scaler = torch.amp.GradScaler("cuda", init_scale=AMP_SCALE, growth_interval=1 << 30)
+    scaler.scale(torch.zeros((), device=DEV))
+    if way == "fused":
+        opt = torch.optim.Adam(spec, lr=LR, fused=True)
+    else:
+        opt = zest_optim.Adam(spec, lr=LR, max_grad_norm=1.0, amp_scaling=way == "amp")
+
+    def step():
+        if way != "amp":
+            scaler.unscale_(opt)
+        if way == "fused":
+            torch.nn.utils.clip_grad_norm_(flat, 1.0)
+        scaler.step(opt)
+        scaler.update()
+    return step
+
+
+def amp_leg(a, groups):
+    steps = {w: build_amp(w.split("_")[0], groups, 0) for w in AMP_WAYS}
+    for w in AMP_WAYS:
+        for _ in range(a.warmup):
+            steps[w]()
+    torch.cuda.synchronize()
+    total = {w: 0.0 for w in AMP_WAYS}
+    done = 0
+    while done < a.iters:
+        n_it = min(a.block, a.iters - done)
+        for w in AMP_WAYS:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n_it):
+                steps[w]()
+            torch.cuda.synchronize()                         # once per block: a synchronise inside a step costs its overlap
+            total[w] += time.perf_counter() - t0
+        done += n_it
+    ms = {w: 1e3 * total[w] / a.iters for w in AMP_WAYS}
+    spread = abs(ms["generic"] - ms["generic_again"])
+    gain = min(ms["generic"], ms["generic_again"]) - ms["amp"]
+    shapes = groups[0] + groups[1]
+    return dict(tensors=len(shapes), elements=sum(int(torch.Size(s).numel()) for s in shapes), scale=AMP_SCALE,
+                ms_per_iteration={k: round(v, 4) for k, v in ms.items()}, generic_spread_ms=round(spread, 4),
+                gain_over_generic_ms=round(gain, 4), amp_faster_than_generic_by_more_than_spread=bool(gain > spread),
+                gain_over_fused_ms=round(ms["fused"] - ms["amp"], 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
     ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--loop", type=int, default=0, help="run only zest_optim.Adam with the clip this many times on each set")
+    ap.add_argument("--amp", action="store_true", help="the GradScaler leg on the generator's parameters instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -90,6 +163,15 @@ def main():
         return
     if a.iters < 200:
         ap.error("--iters must be at least 200")
+    if a.amp:
+        out = dict(bench="optimizer_step_amp", iters=a.iters, block=a.block, warmup=a.warmup, lr=LR, device=torch.cuda.get_device_name(0),
+                   sets={"generator": amp_leg(a, sets["generator"])})
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     out = dict(bench="optimizer_step", iters=a.iters, block=a.block, warmup=a.warmup, lr=LR, device=torch.cuda.get_device_name(0), sets={})
     for name, groups in sets.items():
         shapes = groups[0] + groups[1]

@@ -15,6 +15,14 @@
 // offset in it.  What does change, the gradient addresses (zero_grad(set_to_none=True) frees them every step) and the
 // per-group, per-t scalars, travels in the launch's argument block: no copy, nothing to synchronise.  The block holds
 // kMaxTensors addresses and kMaxSlots rows of scalars; a step with more of either is cut into more launches.
+//
+// The update kernel is a template on the mode.  AMP = false is the step above.  AMP = true (zest_adam_step_amp) speaks a
+// GradScaler's protocol without a host read: the gradients are applied as g / scale, the step is skipped when found_inf
+// is non-zero or (skip_nonfinite) the norm is not finite, and, since the host cannot know which steps were skipped, the
+// step count lives on the device: the scalars travel raw (lr, b1, b2, eps, 1 - b1, 1 - b2 and the host's count of
+// ATTEMPTED steps, as doubles), and one thread per row computes step_size and rbc2 in double from
+// t = t_host - skipped into LDS.  `skipped` is two ints: the step of parity k reads skipped[k] in every workgroup and
+// thread 0 of workgroup 0 of the first update launch alone writes skipped[k ^ 1]; nothing reads what the step writes.
 #include "zest_common.cuh"
 
 namespace {
@@ -30,6 +38,8 @@ enum { T_P, T_M, T_V, T_N, T_SLOT };
 static_assert(T_SLOT + 1 == ZEST_ADAM_TENSOR_COLS, "ZEST_ADAM_TENSOR_COLS");
 enum { S_STEP, S_RBC2, S_EPS, S_OMB1, S_B2, S_OMB2 };
 static_assert(S_OMB2 + 1 == ZEST_ADAM_SCALARS, "ZEST_ADAM_SCALARS");
+enum { R_LR, R_B1, R_B2, R_EPS, R_OMB1, R_OMB2, R_T };
+static_assert(R_T + 1 == ZEST_ADAM_RAW_SCALARS, "ZEST_ADAM_RAW_SCALARS");
 static_assert(kChunk % 4 == 0, "a chunk is whole quads");
 
 struct Grads {
@@ -38,6 +48,24 @@ struct Grads {
 
 struct Slots {
     float s[kMaxSlots][ZEST_ADAM_SCALARS];
+};
+
+// the second argument of the update kernel: the finished scalars, or what the device makes them from
+struct Amp {
+    double raw[kMaxSlots][ZEST_ADAM_RAW_SCALARS];
+    const float *grad_scale, *found_inf;                    // one value each, or NULL
+    const int *skipped_in;                                  // skipped[parity]
+    int *skipped_out;                                       // skipped[parity ^ 1] in the first update launch, else NULL
+    int n_slots, clip, skip_nonfinite;
+};
+
+template <bool AMP>
+struct SlotArg {
+    typedef Slots type;
+};
+template <>
+struct SlotArg<true> {
+    typedef Amp type;
 };
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -134,27 +162,76 @@ __device__ __forceinline__ void chunk_update(const float *g, float *p, float *m,
     }
 }
 
+// b^t for an integer t >= 1 by repeated squaring, in double (at most 31 squarings)
+__device__ __forceinline__ double ipow(double b, int t) {
+    double r = 1.0;
+    for (; t > 0; t >>= 1, b *= b)
+        if (t & 1) r *= b;
+    return r;
+}
+
+// the sum of the n_partial sums of squares, in double, in one fixed order whatever the workgroup: a thread its strided
+// share in index order, the lanes of a wave by butterfly, the waves in turn
+__device__ __forceinline__ double total_sumsq(const float *__restrict__ partial, long long n_partial, double *wave_total) {
+    const int tid = threadIdx.x;
+    double a = 0.0;
+    for (long long i = tid; i < n_partial; i += kThreads) a += (double)partial[i];
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) a += __shfl_xor(a, w, 64);
+    if ((tid & 63) == 0) wave_total[tid >> 6] = a;
+    __syncthreads();
+    double total = 0.0;
+    for (int w = 0; w < kWaves; w++) total += wave_total[w];
+    return total;
+}
+
 // the update of the chunks [c0, c1).  partial: NULL with the clip off; else the n_partial sums of squares of EVERY chunk
 // of the step, which each workgroup adds in double in the same order (a thread its strided share in index order, the
 // lanes of a wave by butterfly, the waves in turn), so that every workgroup of every launch holds the same coefficient.
-__global__ __launch_bounds__(kThreads) void adam_update_kernel(Grads grads, Slots slots, const long long *__restrict__ tens,
+// AMP: see the head of the file.  Every workgroup of every launch of a step reads the same scale, found_inf, sums and
+// counter, so all of them take the same decision; a skipped step stores nothing but the norm and the counter.
+template <bool AMP>
+__global__ __launch_bounds__(kThreads) void adam_update_kernel(Grads grads, typename SlotArg<AMP>::type slots,
+                                                                const long long *__restrict__ tens,
                                                                 const int *__restrict__ chunk_tensor,
                                                                 const long long *__restrict__ chunk_offset, int t0, long long c0,
                                                                 long long c1, const float *__restrict__ partial,
                                                                 long long n_partial, float max_norm, float *__restrict__ norm_out) {
     __shared__ double wave_total[kWaves];
+    __shared__ float made[AMP ? kMaxSlots : 1][ZEST_ADAM_SCALARS];
     const int tid = threadIdx.x;
     float coef = 1.0f;
-    if (partial) {
-        double a = 0.0;
-        for (long long i = tid; i < n_partial; i += kThreads) a += (double)partial[i];
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) a += __shfl_xor(a, w, 64);
-        if ((tid & 63) == 0) wave_total[tid >> 6] = a;
+    if constexpr (AMP) {
+        const float inv = slots.grad_scale ? (float)(1.0 / (double)slots.grad_scale[0]) : 1.0f;
+        bool skip = slots.found_inf && slots.found_inf[0] != 0.0f;
+        const int skipped = slots.skipped_in[0];
+        double mult = (double)inv;
+        if (partial) {
+            const double norm = (double)inv * sqrt(total_sumsq(partial, n_partial, wave_total));    // of the unscaled gradients
+            if (slots.clip) {
+                const double c = (double)max_norm / (norm + 1e-6);
+                if (!(c > 1.0)) mult = (double)inv * c;      // a NaN norm gives a NaN multiplier, as torch's clamp does
+            }
+            if (slots.skip_nonfinite && !(fabs(norm) <= 1.7976931348623157e308)) skip = true;
+            if (norm_out && blockIdx.x == 0 && tid == 0) *norm_out = (float)norm;
+        }
+        coef = (float)mult;
+        if (slots.skipped_out && blockIdx.x == 0 && tid == 0) *slots.skipped_out = skipped + (skip ? 1 : 0);
+        if (skip) return;                                   // the same in every thread of every workgroup of the step
+        if (tid < slots.n_slots) {
+            const double *r = slots.raw[tid];
+            int t = (int)r[R_T] - skipped;
+            t = t < 1 ? 1 : t;
+            made[tid][S_STEP] = (float)(r[R_LR] / (1.0 - ipow(r[R_B1], t)));
+            made[tid][S_RBC2] = (float)(1.0 / sqrt(1.0 - ipow(r[R_B2], t)));
+            made[tid][S_EPS] = (float)r[R_EPS];
+            made[tid][S_OMB1] = (float)r[R_OMB1];
+            made[tid][S_B2] = (float)r[R_B2];
+            made[tid][S_OMB2] = (float)r[R_OMB2];
+        }
         __syncthreads();
-        double total = 0.0;
-        for (int w = 0; w < kWaves; w++) total += wave_total[w];
-        const double norm = sqrt(total), c = (double)max_norm / (norm + 1e-6);
+    } else if (partial) {
+        const double norm = sqrt(total_sumsq(partial, n_partial, wave_total)), c = (double)max_norm / (norm + 1e-6);
         coef = c > 1.0 ? 1.0f : (float)c;                   // a NaN norm gives a NaN coefficient, as torch's clamp does
         if (norm_out && blockIdx.x == 0 && tid == 0) *norm_out = (float)norm;
     }
@@ -163,7 +240,11 @@ __global__ __launch_bounds__(kThreads) void adam_update_kernel(Grads grads, Slot
         const long long *row = tens + (long long)k.tensor * ZEST_ADAM_TENSOR_COLS;
         const float *g = grads.g[k.tensor - t0] + k.offset;
         float *p = (float *)row[T_P] + k.offset, *m = (float *)row[T_M] + k.offset, *v = (float *)row[T_V] + k.offset;
-        const float *s = slots.s[uniform((int)row[T_SLOT])];
+        const float *s;
+        if constexpr (AMP)
+            s = made[uniform((int)row[T_SLOT])];
+        else
+            s = slots.s[uniform((int)row[T_SLOT])];
         if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0)
             chunk_update<true>(g, p, m, v, k.n, coef, s);
         else
@@ -210,15 +291,25 @@ extern "C" size_t zest_adam_work_bytes(long long n_chunks) {
     return (size_t)(n_chunks > 0 ? n_chunks : 1) * sizeof(float);
 }
 
-extern "C" int zest_adam_step(const long long *tensors, const int *chunk_tensor, const long long *chunk_offset, int n_launches,
-                              const int *launch_tensor, const long long *launch_chunk, const void *const *grads,
-                              const float *scalars, int clip, float max_norm, void *work, size_t work_bytes,
-                              float *norm_out, void *stream) {
-    const char *who = "zest_adam_step";
+// the checks and launches of both entries; amp: NULL for zest_adam_step
+struct AmpHost {
+    const double *raw;
+    const int *launch_slots;
+    const float *grad_scale, *found_inf;
+    int skip_nonfinite;
+    int *skipped;
+    int parity;
+};
+
+static int adam_step_launch(const char *who, const long long *tensors, const int *chunk_tensor, const long long *chunk_offset,
+                            int n_launches, const int *launch_tensor, const long long *launch_chunk, const void *const *grads,
+                            const float *scalars, int clip, float max_norm, void *work, size_t work_bytes, float *norm_out,
+                            const AmpHost *amp, void *stream) {
     ZEST_CHECK_ARG(n_launches >= 0, "%s: n_launches=%d", who, n_launches);
     if (n_launches == 0) return 0;
     ZEST_CHECK_ARG(tensors && chunk_tensor && chunk_offset, "%s: null tensor or chunk table", who);
-    ZEST_CHECK_ARG(launch_tensor && launch_chunk && grads && scalars, "%s: null launch bounds, gradient table or scalars", who);
+    ZEST_CHECK_ARG(launch_tensor && launch_chunk && grads && (amp ? (const void *)amp->raw : (const void *)scalars),
+                   "%s: null launch bounds, gradient table or scalars", who);
     ZEST_CHECK_ARG(launch_tensor[0] == 0 && launch_chunk[0] == 0, "%s: the launch bounds do not start at 0", who);
     for (int l = 0; l < n_launches; l++) {
         const int nt = launch_tensor[l + 1] - launch_tensor[l];
@@ -228,16 +319,31 @@ extern "C" int zest_adam_step(const long long *tensors, const int *chunk_tensor,
     const int n_tensors = launch_tensor[n_launches];
     const long long n_chunks = launch_chunk[n_launches];
     for (int t = 0; t < n_tensors; t++) ZEST_CHECK_ARG(grads[t], "%s: gradient %d is null", who, t);
-    if (clip) {
+    if (clip)
         ZEST_CHECK_ARG(max_norm >= 0.0f && max_norm <= 3.0e38f, "%s: max_norm %g is not a finite value >= 0", who, (double)max_norm);
-        ZEST_CHECK_ARG(work && norm_out, "%s: null work buffer or norm with the clip on", who);
+    const bool sums = clip || (amp && amp->skip_nonfinite);  // the first launch: for the clip, or to see a norm that is not finite
+    if (sums) {
+        ZEST_CHECK_ARG(work && norm_out, "%s: null work buffer or norm with the clip%s on", who, amp ? " or skip_nonfinite" : "");
         ZEST_CHECK_ARG(work_bytes >= (size_t)n_chunks * sizeof(float), "%s: work buffer of %zu bytes, %zu needed", who, work_bytes,
                        (size_t)n_chunks * sizeof(float));
     }
-    float *partial = clip ? (float *)work : nullptr;
+    if (amp) {
+        ZEST_CHECK_ARG(amp->skipped, "%s: null skipped counter", who);
+        ZEST_CHECK_ARG(amp->parity == 0 || amp->parity == 1, "%s: parity %d is not 0 or 1", who, amp->parity);
+        ZEST_CHECK_ARG(amp->launch_slots, "%s: null launch_slots", who);
+        for (int l = 0; l < n_launches; l++) {
+            const int ns = amp->launch_slots[l];
+            ZEST_CHECK_ARG(ns >= 1 && ns <= kMaxSlots, "%s: launch %d uses %d rows of scalars, 1..%d fit", who, l, ns, kMaxSlots);
+            for (int k = 0; k < ns; k++) {
+                const double th = amp->raw[((size_t)l * kMaxSlots + k) * ZEST_ADAM_RAW_SCALARS + R_T];
+                ZEST_CHECK_ARG(th >= 1.0 && th <= 2147483647.0 && th == (double)(int)th,
+                               "%s: t_host %g of launch %d, row %d is not a whole number >= 1", who, th, l, k);
+            }
+        }
+    }
+    float *partial = sums ? (float *)work : nullptr;
     Grads g;
-    Slots s;
-    for (int pass = clip ? 0 : 1; pass < 2; pass++) {
+    for (int pass = sums ? 0 : 1; pass < 2; pass++) {
         for (int l = 0; l < n_launches; l++) {
             const int t0 = launch_tensor[l], nt = launch_tensor[l + 1] - t0;
             const long long c0 = launch_chunk[l], c1 = launch_chunk[l + 1];
@@ -246,14 +352,45 @@ extern "C" int zest_adam_step(const long long *tensors, const int *chunk_tensor,
             if (pass == 0) {
                 hipLaunchKernelGGL(adam_sumsq_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, g, tensors, chunk_tensor,
                                    chunk_offset, t0, c0, c1, partial);
+            } else if (amp) {
+                Amp a;
+                for (int k = 0; k < kMaxSlots; k++)
+                    for (int j = 0; j < ZEST_ADAM_RAW_SCALARS; j++)
+                        a.raw[k][j] = amp->raw[((size_t)l * kMaxSlots + k) * ZEST_ADAM_RAW_SCALARS + j];
+                a.grad_scale = amp->grad_scale, a.found_inf = amp->found_inf;
+                a.skipped_in = amp->skipped + amp->parity;
+                a.skipped_out = l == 0 ? amp->skipped + (amp->parity ^ 1) : nullptr;    // once per step, not per launch
+                a.n_slots = amp->launch_slots[l], a.clip = clip != 0, a.skip_nonfinite = amp->skip_nonfinite != 0;
+                hipLaunchKernelGGL(adam_update_kernel<true>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, g, a, tensors,
+                                   chunk_tensor, chunk_offset, t0, c0, c1, (const float *)partial, n_chunks, max_norm,
+                                   l == 0 ? norm_out : nullptr);
             } else {
+                Slots s;
                 for (int k = 0; k < kMaxSlots; k++)
                     for (int j = 0; j < ZEST_ADAM_SCALARS; j++) s.s[k][j] = scalars[((size_t)l * kMaxSlots + k) * ZEST_ADAM_SCALARS + j];
-                hipLaunchKernelGGL(adam_update_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, g, s, tensors,
+                hipLaunchKernelGGL(adam_update_kernel<false>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, g, s, tensors,
                                    chunk_tensor, chunk_offset, t0, c0, c1, (const float *)partial, n_chunks, max_norm,
                                    l == 0 ? norm_out : nullptr);
             }
         }
     }
     ZEST_RETURN_LAUNCH(who);
+}
+
+extern "C" int zest_adam_step(const long long *tensors, const int *chunk_tensor, const long long *chunk_offset, int n_launches,
+                              const int *launch_tensor, const long long *launch_chunk, const void *const *grads,
+                              const float *scalars, int clip, float max_norm, void *work, size_t work_bytes,
+                              float *norm_out, void *stream) {
+    return adam_step_launch("zest_adam_step", tensors, chunk_tensor, chunk_offset, n_launches, launch_tensor, launch_chunk, grads,
+                            scalars, clip, max_norm, work, work_bytes, norm_out, nullptr, stream);
+}
+
+extern "C" int zest_adam_step_amp(const long long *tensors, const int *chunk_tensor, const long long *chunk_offset, int n_launches,
+                                  const int *launch_tensor, const long long *launch_chunk, const int *launch_slots,
+                                  const void *const *grads, const double *raw_scalars, int clip, float max_norm, void *work,
+                                  size_t work_bytes, float *norm_out, const float *grad_scale, const float *found_inf,
+                                  int skip_nonfinite, int *skipped, int parity, void *stream) {
+    const AmpHost amp = {raw_scalars, launch_slots, grad_scale, found_inf, skip_nonfinite, skipped, parity};
+    return adam_step_launch("zest_adam_step_amp", tensors, chunk_tensor, chunk_offset, n_launches, launch_tensor, launch_chunk,
+                            grads, nullptr, clip, max_norm, work, work_bytes, norm_out, &amp, stream);
 }

@@ -55,7 +55,8 @@ PERCEPTUAL_NAMES = ("LPIPS",)
 # zest_metrics.psnr / ssim (csrc/image_metrics.hip), before the caller's script does `from kornia.metrics import psnr, ssim`
 METRIC_NAMES = ("psnr", "ssim")
 # opt-in (install(optimizer=True) / ZEST_DROPIN_OPTIMIZER=1): `Adam` of the caller's own `torch.optim` becomes a factory that
-# returns a zest_optim.Adam (csrc/optim.hip) for fp32 parameters on a HIP device and options it builds, else the package's own
+# returns a zest_optim.Adam (csrc/optim.hip) for fp32 parameters on a HIP device and options it builds, else the package's own;
+# with install(optimizer_amp=True) / ZEST_DROPIN_OPTIMIZER_AMP=1 beside it the factory passes amp_scaling=True
 OPTIMIZER_NAMES = ("Adam",)
 _saved = []          # (module, name, had, old) for uninstall()
 
@@ -94,18 +95,20 @@ def _lpips_factory(package_cls):
     return LPIPS
 
 
-def _adam_factory(package_cls):
+def _adam_factory(package_cls, amp=False):
     """-> a callable with torch.optim.Adam's signature: a zest_optim.Adam where every parameter is fp32 on one HIP device
     and the options are ones it builds (zest_optim.refusal), the package's own class otherwise - never an error the
-    package would not have raised.  It is a function: a caller that SUBCLASSES torch.optim.Adam must do so before."""
+    package would not have raised.  It is a function: a caller that SUBCLASSES torch.optim.Adam must do so before.
+    amp: the zest_optim.Adam is built with amp_scaling=True (the package's own class never sees the option)."""
     import zest_optim
+    ours = {"amp_scaling": True} if amp else {}
 
     def Adam(params, *args, **kwargs):
         params = list(params)
         if params and isinstance(params[0], dict):
             params = [dict(g, params=[g["params"]] if hasattr(g["params"], "dtype") else list(g["params"])) for g in params]
         if zest_optim.refusal(params, *args, **kwargs) is None:
-            return zest_optim.Adam(params, *args, **kwargs)
+            return zest_optim.Adam(params, *args, **dict(kwargs, **ours))
         return package_cls(params, *args, **kwargs)
     Adam.__doc__ = "zest_dropin: torch.optim.Adam -> zest_optim.Adam where it is built, else the package's own"
     Adam.__wrapped__ = package_cls
@@ -113,7 +116,8 @@ def _adam_factory(package_cls):
 
 
 def install(reference_dir=None, modules=("utils", "renderer", "networks", "losses"), stub_inplace_abn=True,
-            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False, metrics=False, optimizer=False):
+            sf_losses=False, patch_losses=False, discriminator=False, perceptual=False, metrics=False, optimizer=False,
+            optimizer_amp=False):
     """Import the caller's `modules` (from `reference_dir` if given, else from sys.path as it stands)
     and rebind the rendering path's names in them.  Returns {module name: [rebound names]}.
     sf_losses: also rebind `losses.compute_sf_smooth_loss` and `losses.compute_sf_lke_loss` (off by default:
@@ -129,8 +133,14 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
     parameters on a HIP device and options it builds, and the package's own Adam otherwise (off by default: it stays
     torch's).  A Trainer(gradient_clip_val=...) still clips on its own, in torch; the clip fused into the update is for
     callers who pass max_grad_norm and drop gradient_clip_val.
+    optimizer_amp: with optimizer, the factory builds its zest_optim.Adam with amp_scaling=True, so a GradScaler hands
+    the step its scale and found_inf instead of reading found_inf on the host (off by default: later Lightning releases
+    skip unscale_ and refuse gradient_clip_val for such an optimiser; INTEGRATION.md has the recipe).  ValueError without
+    optimizer.
     Raises ImportError if one of the caller's modules cannot be imported, and RuntimeError if a
     module found under one of those names is this package's own (nothing to overlay)."""
+    if optimizer_amp and not optimizer:
+        raise ValueError("zest_dropin.install: optimizer_amp=True without optimizer=True")
     here = os.path.dirname(os.path.abspath(__file__))
     if reference_dir is not None:
         reference_dir = os.path.abspath(reference_dir)
@@ -178,7 +188,7 @@ def install(reference_dir=None, modules=("utils", "renderer", "networks", "losse
     if optimizer:
         package = importlib.import_module("torch.optim")
         for n in OPTIMIZER_NAMES:
-            _bind(package, n, _adam_factory(getattr(package, n)))
+            _bind(package, n, _adam_factory(getattr(package, n), amp=optimizer_amp))
         done["torch.optim"] = sorted(OPTIMIZER_NAMES)
     return done
 
@@ -203,7 +213,8 @@ def main(argv=None):
               "regularisers of the static step (total_variation_loss, get_disparity_smoothness), ZEST_DROPIN_DISCRIMINATOR=1 "
               "the GRAF patch discriminator (networks.GRAFDiscriminator), ZEST_DROPIN_PERCEPTUAL=1 the LPIPS network "
               "(lpips.LPIPS, AlexNet backbone), ZEST_DROPIN_METRICS=1 the image metrics of the validation and test steps "
-              "(kornia.metrics.psnr, kornia.metrics.ssim), ZEST_DROPIN_OPTIMIZER=1 the optimiser (torch.optim.Adam)")
+              "(kornia.metrics.psnr, kornia.metrics.ssim), ZEST_DROPIN_OPTIMIZER=1 the optimiser (torch.optim.Adam), with "
+              "ZEST_DROPIN_OPTIMIZER_AMP=1 beside it as one that takes a GradScaler's scale and found_inf itself")
         return 0 if argv else 2
     script = os.path.abspath(argv[0])
     install(reference_dir=os.path.dirname(script), sf_losses=os.environ.get("ZEST_DROPIN_SF_LOSSES", "") == "1",
@@ -211,7 +222,8 @@ def main(argv=None):
             discriminator=os.environ.get("ZEST_DROPIN_DISCRIMINATOR", "") == "1",
             perceptual=os.environ.get("ZEST_DROPIN_PERCEPTUAL", "") == "1",
             metrics=os.environ.get("ZEST_DROPIN_METRICS", "") == "1",
-            optimizer=os.environ.get("ZEST_DROPIN_OPTIMIZER", "") == "1")
+            optimizer=os.environ.get("ZEST_DROPIN_OPTIMIZER", "") == "1",
+            optimizer_amp=os.environ.get("ZEST_DROPIN_OPTIMIZER_AMP", "") == "1")
     sys.argv = [script] + argv[1:]
     runpy.run_path(script, run_name="__main__")
     return 0

@@ -108,6 +108,8 @@ _SIGS = {
     "zest_adam_work_bytes": (_sz, [C.c_longlong]),
     "zest_adam_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_vp), C.POINTER(_f), _i, _f,
                             _vp, _sz, _vp, _vp]),
+    "zest_adam_step_amp": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_vp),
+                                C.POINTER(C.c_double), _i, _f, _vp, _sz, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "zest_volume_cost_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -839,6 +841,7 @@ def image_metrics(pred, target, window=5, clamp_pred=False, max_val=1.0, want_ma
 # ------------------------------------------------------------------------ optimiser (csrc/optim.hip)
 ADAM_TENSOR_COLS = 5              # device table row: addresses of p, exp_avg, exp_avg_sq; element count; row of scalars
 ADAM_SCALARS = 6                  # step_size, 1 / sqrt(bias_correction2), eps, 1 - b1, b2, 1 - b2
+ADAM_RAW_SCALARS = 7              # adam_step_amp: lr, b1, b2, eps, 1 - b1, 1 - b2, the host's count of attempted steps
 
 
 def adam_chunk():
@@ -873,9 +876,12 @@ def adam_plan(sizes):
 
 class AdamTable:
     """What zest_adam_step reads that does not change from step to step: the device tables, the launch bounds, the
-    work buffer of the clip; built by adam_table()."""
+    work buffer of the clip; built by adam_table().  What only adam_step_amp needs is made at its first call, so a table
+    that never sees one is what it always was: .skipped, the device counter of skipped steps (int32 [2], None before),
+    .parity, the element of it the next call reads (the current count is skipped[parity]), the host arrays of the raw
+    scalars and of the rows each launch uses."""
     __slots__ = ("device", "n_tensors", "n_chunks", "tensors", "chunk_tensor", "chunk_offset", "n_launches", "launch_tensor",
-                 "launch_chunk", "launch_keys", "work", "work_bytes", "scalars", "stamp")
+                 "launch_chunk", "launch_keys", "work", "work_bytes", "scalars", "stamp", "skipped", "parity", "raw", "launch_slots")
 
 
 def adam_table(params, exp_avgs, exp_avg_sqs, keys):
@@ -887,6 +893,7 @@ def adam_table(params, exp_avgs, exp_avg_sqs, keys):
     if not (len(params) == len(exp_avgs) == len(exp_avg_sqs) == len(keys)):
         raise RuntimeError("zest_hip: %s: %d params, %d exp_avg, %d exp_avg_sq, %d keys" % (who, len(params), len(exp_avgs), len(exp_avg_sqs), len(keys)))
     T = AdamTable()
+    T.skipped, T.parity, T.raw, T.launch_slots = None, 0, None, None
     T.n_tensors = len(params)
     T.device = params[0].device if params else None
     for name, ts in (("param", params), ("exp_avg", exp_avgs), ("exp_avg_sq", exp_avg_sqs)):
@@ -957,6 +964,53 @@ def adam_step(table, grads, scalars, max_norm=None):
                                 table.launch_tensor, table.launch_chunk, ptrs, sc, int(max_norm is not None),
                                 0.0 if max_norm is None else float(max_norm), _ptr(table.work), table.work_bytes, _ptr(norm),
                                 torch.cuda.current_stream(dev).cuda_stream), "zest_adam_step")
+    return norm
+
+
+def adam_step_amp(table, grads, raw_scalars, max_norm=None, grad_scale=None, found_inf=None, skip_nonfinite=False):
+    """adam_step under a GradScaler's protocol, decided on the device (zest_adam_step_amp): no host read.
+    raw_scalars: {key: (lr, b1, b2, eps, 1 - b1, 1 - b2, t_host)} for every key of table.launch_keys, t_host the count of
+    ATTEMPTED steps including this one; the kernel subtracts the table's skipped steps.  grad_scale, found_inf: None, or a
+    one-element fp32 tensor on the table's device: gradients are applied as g / scale; a non-zero found_inf skips the
+    step.  skip_nonfinite: skip also when the unscaled norm is not finite (the norm is then taken also with max_norm None).
+    A skipped step writes nothing to the tensors.  table.skipped[table.parity] is afterwards the device count of skipped
+    steps of this table.
+    -> None (a table without tensors; without max_norm and skip_nonfinite), or the 0-d device tensor of the unscaled,
+    unclipped norm."""
+    who = "adam_step_amp"
+    if len(grads) != table.n_tensors:
+        raise RuntimeError("zest_hip: %s: %d gradients for a table of %d tensors" % (who, len(grads), table.n_tensors))
+    for i, g in enumerate(grads):
+        if not g.is_cuda:
+            raise RuntimeError("zest_hip: grads[%d] is on %s; this path runs only on a HIP device" % (i, g.device))
+    if table.n_tensors == 0:
+        return None
+    dev = table.device
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == 1 and t.device == dev):
+            raise RuntimeError("zest_hip: %s: %s must be a one-element fp32 tensor on %s, got %s" % (
+                who, name, dev, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+    max_s = adam_max_slots()
+    if table.skipped is None:
+        table.skipped = torch.zeros(2, device=dev, dtype=torch.int32)
+        table.parity = 0
+        table.raw = (C.c_double * (table.n_launches * max_s * ADAM_RAW_SCALARS))()
+        table.launch_slots = (_i * table.n_launches)(*[len(keys) for keys in table.launch_keys])
+    ptrs = (_vp * table.n_tensors)(*[g.data_ptr() for g in grads])
+    raw, row = table.raw, max_s * ADAM_RAW_SCALARS
+    for l, keys in enumerate(table.launch_keys):
+        for k, key in enumerate(keys):
+            o = l * row + k * ADAM_RAW_SCALARS
+            raw[o:o + ADAM_RAW_SCALARS] = raw_scalars[key]
+    sums = max_norm is not None or bool(skip_nonfinite)
+    norm = torch.empty((), device=dev, dtype=torch.float32) if sums else None
+    _check(lib().zest_adam_step_amp(_ptr(table.tensors), _ptr(table.chunk_tensor), _ptr(table.chunk_offset), table.n_launches,
+                                    table.launch_tensor, table.launch_chunk, table.launch_slots, ptrs, raw,
+                                    int(max_norm is not None), 0.0 if max_norm is None else float(max_norm), _ptr(table.work),
+                                    table.work_bytes, _ptr(norm), _ptr(grad_scale), _ptr(found_inf), int(bool(skip_nonfinite)),
+                                    table.skipped.data_ptr(), table.parity, torch.cuda.current_stream(dev).cuda_stream),
+           "zest_adam_step_amp")
+    table.parity ^= 1
     return norm
 
 

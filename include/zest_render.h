@@ -97,7 +97,9 @@ int         zest_device_info(int *cu_count, int *clock_khz, char *name, size_t n
  * the sample distances are taken from it instead (the `dists` argument of the reference's
  * raw2outputs, whatever produced it) and rays_dir may be NULL.  noise [R,S] or NULL is
  * added to sigma after scaling by noise_std.  Any output pointer may be NULL.
- * rgb_map [R,3], depth/acc/disp [R], weights/alpha [R,S]. */
+ * rgb_map [R,3], depth/acc/disp [R], weights/alpha [R,S].
+ * disp = 1 / max(1e-10, depth / acc) with the reference's max, which hands a NaN on: a ray with
+ * no accumulated weight (acc == 0, quotient 0 / 0) has disp = NaN, not 1e10. */
 int zest_composite_fwd(const float *raw, const float *z, const float *rays_dir, const float *dists,
                        const float *noise, float noise_std, int white_bkgd,
                        int R, int S,

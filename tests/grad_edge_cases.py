@@ -35,13 +35,14 @@ def rows_close(got, want, lead, name):
     got, want = _np(got), _np(want)
     assert got.shape == want.shape, (name, got.shape, want.shape)
     assert np.isfinite(got).all(), "%s: non-finite entries" % name
+    assert np.isfinite(want).all(), "%s: the reference holds non-finite entries" % name
     nrow = int(np.prod(want.shape[:lead], dtype=np.int64))
     g, w = got.reshape(nrow, -1), want.reshape(nrow, -1)
     scale = np.abs(w).max(1, keepdims=True)
     err = np.abs(g - w)
     dead = scale[:, 0] == 0
     assert (g[dead] == 0).all(), "%s: %d rows with an all-zero reference are not exactly zero" % (name, (g[dead] != 0).any(1).sum())
-    bad = err > REL * scale + REL * np.abs(w)
+    bad = ~(err <= REL * scale + REL * np.abs(w))
     frac = float((err[~dead] / scale[~dead]).max()) if (~dead).any() else 0.0
     assert not bad.any(), "%s: %d/%d outside tolerance in %d rows, worst err / row max %.3g" % (
         name, bad.sum(), bad.size, bad.any(1).sum(), frac)
@@ -54,9 +55,10 @@ def tensor_close(got, want, name, exact_zeros=False):
     got, want = _np(got), _np(want)
     assert got.shape == want.shape, (name, got.shape, want.shape)
     assert np.isfinite(got).all(), "%s: non-finite entries" % name
+    assert np.isfinite(want).all(), "%s: the reference holds non-finite entries" % name
     scale = np.abs(want).max() + 1e-12
     err = np.abs(got - want)
-    bad = err > REL * scale + REL * np.abs(want)
+    bad = ~(err <= REL * scale + REL * np.abs(want))
     assert not bad.any(), "%s: %d/%d outside tolerance, max err %.3g (scale %.3g)" % (name, bad.sum(), bad.size, err.max(), scale)
     if exact_zeros:
         assert (got[want == 0] == 0).all(), "%s: entries with a zero reference are not exactly zero" % name

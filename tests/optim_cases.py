@@ -67,7 +67,11 @@ def judge(got, old, g, t, lr, betas=BETAS, eps=EPS, coef=1.0, where=None, label=
         err = np.abs(np.asarray(have, dtype=np.float64) - want)
         if where is not None:
             err, bound = err[where], np.broadcast_to(bound, want.shape)[where]
-        bad = ~(err <= bound)                                # a NaN is bad
+        # only judged elements count: outside `where` a skipped step may leave a NaN.  Inside it the reference and its
+        # bound must be finite, and a NaN or an infinite error is bad (`~(err <= bound)`, never `err > bound`)
+        assert np.isfinite(bound).all() and np.isfinite(np.asarray(want)[where] if where is not None else want).all(), \
+            "%s %s: the reference or its bound is not finite on a judged element" % (label, name)
+        bad = ~(err <= bound)
         worst[name] = float(np.max(err / np.maximum(bound, 1e-300), initial=0.0)) if err.size and not bad.any() else float("inf")
         assert not bad.any(), "%s %s: %d of %d elements outside the bound, first at %d: error %.3g, bound %.3g" % (
             label, name, int(bad.sum()), bad.size, int(np.argmax(bad)), float(err[np.argmax(bad)]), float(bound[np.argmax(bad)]))

@@ -21,9 +21,11 @@ def gclose(got, want, name, rel=1e-3):
     got = got.detach().double().cpu().numpy() if torch.is_tensor(got) else np.asarray(got, np.float64)
     want = np.asarray(want, np.float64)
     assert got.shape == want.shape, (name, got.shape, want.shape)
+    assert np.isfinite(want).all(), "%s: the reference holds %d non-finite entries" % (name, (~np.isfinite(want)).sum())
+    assert np.isfinite(got).all(), "%s: %d non-finite entries" % (name, (~np.isfinite(got)).sum())
     scale = np.abs(want).max() + 1e-12
     err = np.abs(got - want)
-    bad = err > rel * scale + rel * np.abs(want)
+    bad = ~(err <= rel * scale + rel * np.abs(want))
     assert not bad.any(), "%s: %d/%d outside tolerance, max err %.3g (scale %.3g)" % (
         name, bad.sum(), bad.size, err.max(), scale)
 

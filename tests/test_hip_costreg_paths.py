@@ -128,12 +128,13 @@ def check_elements(name, got, want, A, eps, rows_per_tile=None):
     block and lane, channel; for a convolution also the row within its group; the parity class of a transposed one)."""
     err = (got.double() - want).abs()
     bound = eps * A + 2.0 ** -23 * want.abs()
+    assert bool(torch.isfinite(want).all()) and bool(torch.isfinite(A).all()), "%s: the reference or its magnitude is not finite" % name
     ratio = float((err / (eps * A).clamp_min(1e-300))[A > 0].max())
     print("RATIO %-58s max |err| / (eps A) = %.4f   (eps %.3e)" % (name, ratio, eps))
-    bad = err > bound
+    bad = ~(err <= bound)                                    # not `err > bound`: a NaN error is bad
     if bool(bad.any()):
         n_bad = int(bad.sum())
-        over = torch.where(bad, err / bound.clamp_min(1e-300), torch.zeros_like(err))
+        over = torch.where(bad, (err / bound.clamp_min(1e-300)).nan_to_num(nan=float("inf"), posinf=float("inf")), torch.zeros_like(err))
         z, y, x, c = (int(v) for v in torch.unravel_index(over.argmax(), over.shape))
         idx = bad.nonzero()
         rows, slices = torch.unique(idx[:, 1])[:24].tolist(), torch.unique(idx[:, 0])[:24].tolist()

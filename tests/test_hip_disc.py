@@ -34,16 +34,17 @@ def _steps(B, imsize, ndf, seed, digests=False):
 
 def _close_grad(got, want, name):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and not np.isnan(got).any(), name
+    assert got.shape == want.shape and np.isfinite(got).all(), name
     assert np.abs(want).max() > 0, name
     close(got, want, atol=ATOL * np.abs(want).max(), name=name)
 
 
 def _close_l2(got, want, name):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and not np.isnan(got).any(), name
+    assert got.shape == want.shape and np.isfinite(got).all(), name
+    assert np.isfinite(want).all() and np.linalg.norm(want) > 0, name
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
-    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)
+    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)               # false for a NaN
 
 
 def _compare(got, want, imsize, ndf, name, digests=False):
@@ -56,13 +57,15 @@ def _compare(got, want, imsize, ndf, name, digests=False):
         elif k.startswith("disc__grad__"):
             _close_grad(v, w, tag)
         elif k.startswith("disc__grad_norm__"):
+            assert np.isfinite(v) and np.isfinite(w), (tag, v, w)
             assert abs(v - w) <= RTOL * w, (tag, v, w)
         elif k.startswith("disc__grad_dots__"):
             i = int(k.rsplit("__", 1)[1])
             shape = dc.state(imsize, ndf, 0)["main.%d.weight_orig" % i].shape
             d_norm = np.linalg.norm(dc.directions(imsize, ndf, i, shape).reshape(dc.N_DIRS, -1), axis=1)
             bound = RTOL * np.asarray(want["disc__grad_norm__%d" % i], np.float64) * d_norm
-            assert (np.abs(v - w) <= bound).all(), (tag, v, w, bound)
+            assert np.isfinite(v).all() and np.isfinite(w).all() and np.isfinite(bound).all(), (tag, v, w, bound)
+            assert not (~(np.abs(v - w) <= bound)).any(), (tag, v, w, bound)
         else:
             close(np.atleast_1d(v), np.atleast_1d(w), name=tag)
 

@@ -31,6 +31,15 @@ def G(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
+def elements_close(got, want):
+    """1e-4 abs + 1e-3 rel on every element against a finite float64 reference; a non-finite error is outside it."""
+    assert np.isfinite(want).all()
+    err = np.abs(got - want)
+    bad = ~(err <= ATOL + RTOL * np.abs(want))
+    assert not bad.any(), "%d/%d outside 1e-4 + 1e-3 rel (%d not finite), max err %.3g" % (
+        bad.sum(), bad.size, (~np.isfinite(got)).sum(), np.nanmax(err))
+
+
 def _state(Fd, use_mvs, seed, lively):
     return zs.fill_mlp_state(zs.mlp_layout(gc.PE_PTS, gc.PE_DIR, Fd, False, True, use_mvs), seed, lively=lively)
 
@@ -57,8 +66,7 @@ def test_fold_arithmetic_with_bias_meets_fp32_tolerance_against_float64(hip, use
     print("fold arithmetic (%s): max err %.3g, rms err %.3g, max |ref| %.3g, rgb spread %.3g"
           % ("features" if use_mvs else "no features", err.max(), np.sqrt((err ** 2).mean()), np.abs(want).max(),
              want[:, :3].std()))
-    bad = err > ATOL + RTOL * np.abs(want)
-    assert not bad.any(), "%d/%d outside 1e-4 + 1e-3 rel, max err %.3g" % (bad.sum(), bad.size, err.max())
+    elements_close(got, want)
     # the check has teeth: without the Wvh bf term the rgb outputs would sit far outside the tolerance
     sd = orun.state_t(state, torch.float64)
     sd["nerf.feature_linear.bias"] = torch.zeros(256, dtype=torch.float64)

@@ -27,10 +27,12 @@ def _dev(a):
 
 def _close(got, want, what):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert np.isfinite(want).all() and np.isfinite(got).all(), "%s: non-finite entries" % what
     err = np.abs(got - want)
     bound = ATOL + RTOL * np.abs(want)
     print("%s: worst error / bound = %.4f" % (what, float((err / bound).max())))
-    assert (err <= bound).all(), (what, float((err / bound).max()))
+    assert not (~(err <= bound)).any(), (what, float((err / bound).max()))
 
 
 def _check_case(case, ws=5):

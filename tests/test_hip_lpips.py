@@ -29,9 +29,10 @@ def _net(st):
 
 def _layers_close(got, want, name):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and (want > 0).all(), name
+    assert got.shape == want.shape and (want > 0).all() and np.isfinite(want).all(), name
+    assert np.isfinite(got).all(), "%s: non-finite layer terms %s" % (name, got)
     rel = np.abs(got - want) / want
-    assert (rel <= RTOL).all(), "%s: per-layer relative error %s" % (name, rel)
+    assert not (~(rel <= RTOL)).any(), "%s: per-layer relative error %s" % (name, rel)
 
 
 def _grad_close(got, want, name):
@@ -44,8 +45,9 @@ def _grad_close(got, want, name):
 def _l2_close(got, want, name):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     assert got.shape == want.shape and np.isfinite(got).all(), name
+    assert np.isfinite(want).all() and np.linalg.norm(want) > 0, name
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
-    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)
+    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)               # false for a NaN
 
 
 def _run(P, in0, in1, backward=True, **kw):

@@ -20,16 +20,35 @@ def G(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
+def same_nonfinite(got, want):
+    """Where two float64 arrays hold the same non-finite value: NaN in both, or the same infinity."""
+    return (np.isnan(got) & np.isnan(want)) | (np.isinf(want) & (got == want))
+
+
+def wild(got, want):
+    """Where exactly one side is non-finite, or both are and differ: never within any tolerance."""
+    return ~(np.isfinite(got) & np.isfinite(want)) & ~same_nonfinite(got, want)
+
+
 def close(got, want, atol=ATOL, rtol=RTOL, name=""):
+    """Every element within atol + rtol |want|.  A NaN or an infinity passes only against the same value at the same
+    position of `want` (a fixture may pin one); a non-finite error is outside every tolerance."""
     got = got.detach().double().cpu().numpy() if torch.is_tensor(got) else np.asarray(got, np.float64)
     want = np.asarray(want, np.float64)
     assert got.shape == want.shape, (name, got.shape, want.shape)
-    both_nan = np.isnan(got) & np.isnan(want)
-    err = np.where(both_nan, 0, np.abs(got - want))
-    tol = atol + rtol * np.abs(np.where(both_nan, 0, want))
-    bad = err > tol
-    assert not bad.any(), "%s: %d/%d outside tolerance, max err %.3g at |ref| %.3g" % (
-        name, bad.sum(), bad.size, err.max(), np.abs(want).flat[np.nanargmax(err)])
+    # callers scale atol by max|want|: an infinity in the reference must not become an infinite tolerance
+    assert np.all(np.isfinite(atol)) and np.all(np.isfinite(rtol)), (name, atol, rtol)
+    same = same_nonfinite(got, want)
+    with np.errstate(invalid="ignore"):
+        err = np.where(same, 0.0, np.abs(got - want))
+    tol = atol + rtol * np.where(np.isfinite(want), np.abs(want), 0.0)
+    bad = ~(err <= tol)                                   # not `err > tol`: a NaN error is bad
+    if bad.any():
+        first = np.unravel_index(np.flatnonzero(bad)[0], bad.shape) if bad.ndim else ()
+        finite = np.where(np.isfinite(err), err, -1.0)
+        raise AssertionError("%s: %d/%d outside tolerance (%d not finite), max finite err %.3g at |ref| %.3g; first at %s: got %r want %r" % (
+            name, bad.sum(), bad.size, wild(got, want).sum(), finite.max(), np.abs(want).flat[finite.argmax()],
+            tuple(int(i) for i in first), float(got[first]), float(want[first])))
 
 
 @pytest.mark.parametrize("case", ["composite", "composite_white"])
@@ -40,6 +59,12 @@ def test_composite(hip, case):
                            white_bkgd=gc.CASES[case].get("white_bkgd", False))
     for n, v in zip(("rgb_map", "disp_map", "acc_map", "weights", "depth_map", "alpha"), r):
         close(v, gold[n], name=n)
+    # ray 1 has sigma <= 0 everywhere: no weight, and the reference's disparity 1 / max(1e-10, 0 / 0) is NaN there only
+    dead = np.arange(inp["raw"].shape[0]) == 1
+    assert np.array_equal(np.isnan(gold["disp_map"]), dead) and float(gold["acc_map"][1]) == 0.0
+    assert np.array_equal(np.isnan(r[1].cpu().numpy()), dead) and float(r[2][1]) == 0.0
+    for n, v in zip(("rgb_map", "acc_map", "weights", "depth_map", "alpha"), (r[0], r[2], r[3], r[4], r[5])):
+        assert np.isfinite(gold[n]).all() and bool(torch.isfinite(v).all()), n
 
 
 def test_composite_noise_and_properties(hip):

@@ -143,7 +143,8 @@ def test_rendering_trains_in_bf16_mode(hip, case):
     for k in ("rgb_map", "depth_map", "rgb_map_ref", "depth_map_ref", "rgb_map_ref_dy", "depth_map_ref_dy"):
         if k in m32:        # (maps behind the scene-flow chain are compared through the gradients' alignment only)
             err = np.abs(m16[k] - m32[k]).reshape(m32[k].shape[1], -1).max(-1)
-            assert (err > 3e-2 * max(1.0, np.abs(m32[k]).max())).sum() <= 1, (k, err.max())
+            assert np.isfinite(m16[k]).all() and np.isfinite(m32[k]).all(), k       # the one excused ray is a finite flip
+            assert (~(err <= 3e-2 * max(1.0, np.abs(m32[k]).max()))).sum() <= 1, (k, err.max())
     if not sf:
         assert abs(l16 - l32) <= 1e-2 * max(1.0, abs(l32)), (l16, l32)
     for k in g32:

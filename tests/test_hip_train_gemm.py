@@ -59,10 +59,14 @@ def check_bound(zh, op, a, b, got, c0=None, name=""):
     ref, mag = tg.ref64(A, B)
     if c0 is not None:
         ref, mag = ref + c0, mag + np.abs(c0)
+    assert np.all(np.isfinite(ref)) and np.all(np.isfinite(mag)), name
+    # the library's error sets the bound: a non-finite library result would make it infinite, or NaN
+    assert np.all(np.isfinite(got[zh.GEMM_LIBRARY])), "%s: the library result is not finite" % name
+    assert np.all(np.isfinite(got[zh.GEMM_SPLIT_BF16])), name
     r_lib, r_split = tg.ratio(got[zh.GEMM_LIBRARY], ref, mag), tg.ratio(got[zh.GEMM_SPLIT_BF16], ref, mag)
     c = tg.bound_factor(r_lib)
     print("%s: library %.3g  split %.3g  bound %.3g" % (name, r_lib, r_split, c))
-    assert np.all(np.isfinite(got[zh.GEMM_SPLIT_BF16])), name
+    assert np.isfinite(c), "%s: bound %r from the library's %r" % (name, c, r_lib)
     assert r_split <= c, "%s: split %.3g > bound %.3g (library %.3g)" % (name, r_split, c, r_lib)
 
 

@@ -69,7 +69,12 @@ __global__ __launch_bounds__(kWavesPerBlock *ZEST_WAVE) void composite_kernel(
         }
         if (depth_map) depth_map[r] = a_d;
         if (acc_map) acc_map[r] = a_w;
-        if (disp_map) disp_map[r] = 1.0f / fmaxf(1e-10f, a_d / a_w);
+        if (disp_map) {
+            // a ray with no accumulated weight has the quotient 0 / 0: the reference's torch.max hands the NaN on
+            // (renderer.py:153, pinned by the composite fixtures), fmaxf would drop it and give 1e10
+            const float q = a_d / a_w;
+            disp_map[r] = 1.0f / (q != q ? q : fmaxf(1e-10f, q));
+        }
     }
 }
 

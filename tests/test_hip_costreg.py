@@ -259,7 +259,8 @@ def test_regularisation_net_trains_through_the_hip_forward(hip, passes, tol):
     gradient of ITS forward, and the relative L2 difference of two such gradients is sqrt(flipped fraction) ~ 5e-3
     (layers without a flipped element agree to 1e-5).  Bounds: relative L2 error per gradient tensor 2e-2 with
     split-bf16 operands, 0.35 with bf16 operands (against the library's bf16 autocast path, itself that far from
-    fp32)."""
+    fp32).  That bound is the distance between two forwards; the backward itself is judged at its forward's own values
+    in test_hip_builder_grads.py."""
     import zest_autograd
     import zest_networks as networks
     torch.manual_seed(21)
@@ -290,7 +291,9 @@ def test_regularisation_net_trains_through_the_hip_forward(hip, passes, tol):
 
 @pytest.mark.parametrize("passes,tol", [(3, 2e-2), (1, 0.35)])
 def test_feature_pyramid_trains_through_the_hip_forward(hip, passes, tol):
-    """zest_autograd.FeatureFn against plain autograd through the library modules; bounds as for the regularisation net."""
+    """zest_autograd.FeatureFn against plain autograd through the library modules; bounds as for the regularisation net:
+    the distance between two forwards - the backward itself is judged at its forward's own values in
+    test_hip_builder_grads.py."""
     import zest_autograd
     import zest_networks as networks
     torch.manual_seed(23)

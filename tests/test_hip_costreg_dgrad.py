@@ -92,7 +92,9 @@ def test_through_the_regularisation_net(hip):
     with hip_dgrad on, two with it off.  The cost gradient: (1, 41, 16, 16, 24) fp32, relative L2 difference
     below 1e-2 (the library rounds its result to bf16, 2^-9 per element).  Every parameter gradient: at most 1e-6
     relative L2 plus four times what the two off runs differ by.  The saved tensors are the same in number.  With the
-    weight-gradient kernel on as well the cost gradient is the same, bit for bit.  passes = 3 ignores the switch."""
+    weight-gradient kernel on as well the cost gradient is the same, bit for bit.  passes = 3 ignores the switch.
+    The bounds here are the distance between two runs; the backward itself is judged at its forward's own values in
+    test_hip_builder_grads.py."""
     import zest_autograd
     import zest_networks as networks
     torch.manual_seed(21)

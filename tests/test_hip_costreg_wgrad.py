@@ -97,7 +97,9 @@ def test_through_the_regularisation_net(hip):
     with the switch on, two with it off.  conv0's weight gradient: relative L2 difference below 1e-2 (the library
     rounds its result to bf16, 2^-9 per element, and sums in another order).  Every other gradient, the one towards
     the cost volume included: at most 1e-6 relative L2 plus four times what the two off runs differ by.  With the
-    switch off the saved tensors are those of before: one fewer than with it on (the channels-last cost volume)."""
+    switch off the saved tensors are those of before: one fewer than with it on (the channels-last cost volume).
+    The bounds here are the distance between two runs; the backward itself is judged at its forward's own values in
+    test_hip_builder_grads.py."""
     import zest_autograd
     import zest_networks as networks
     torch.manual_seed(21)

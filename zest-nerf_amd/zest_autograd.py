@@ -540,14 +540,46 @@ def _kept_layers(ctx):
     return t[0], t[1:1 + n], t[1 + n:1 + 2 * n], t[1 + 2 * n:1 + 3 * n], t[1 + 3 * n:], extra
 
 
+def _dgrad_as_forward(g, w, stride, padding, x_spatial):
+    """The data gradient of a convolution (weight [cout,cin,k,..], no dilation, one group) as a FORWARD 3-D convolution:
+    g zero-dilated by the stride, against the weight with its two channel axes exchanged and its taps mirrored, padding
+    k - 1 - padding; where the windows do not reach the input's end (stride 2 on an even extent) g is padded with zeros
+    at the end, so that the result has the input's extents and every position sums exactly the taps that covered it.  A
+    2-D layer runs as a 3-D one of depth 1.  Why: the library's bf16 backward-data kernels do not round their fp32 sums to
+    nearest - a 2-D result is truncated (twice the rounding error, half the elements one ulp low), a 3-D one carries
+    1.4 times the rounding error - while its 3-D forward kernels do (tests/test_hip_builder_grads.py)."""
+    nd = w.dim() - 2
+    k, q = w.shape[2], w.shape[2] - 1 - padding
+    wt = w.transpose(0, 1).flip(*range(2, 2 + nd))
+    if stride > 1:
+        gd = g.new_zeros(g.shape[:2] + tuple((m - 1) * stride + 1 for m in g.shape[2:]))
+        gd[(slice(None), slice(None)) + (slice(None, None, stride),) * nd] = g
+        g = gd
+    short = [n - (m + 2 * q - k + 1) for n, m in zip(x_spatial, g.shape[2:])]
+    if any(short):
+        g = torch.nn.functional.pad(g, [v for s in reversed(short) for v in (0, s)])
+    if nd == 2:
+        return torch.nn.functional.conv3d(g.unsqueeze(2), wt.unsqueeze(2), padding=(0, q, q)).squeeze(2)
+    return torch.nn.functional.conv3d(g, wt, padding=q)
+
+
 def _conv_bwd(g_r, x, w, low, stride, padding, transposed, mask):
     """The library's convolution backward (no bias, no dilation, one group; 2-D or 3-D by the weight's rank), operands
-    cast to `low` (ctx.low) unless None -> (g_x, g_w) in fp32, None where `mask` = [input, weight, False] does not ask."""
+    cast to `low` (ctx.low) unless None -> (g_x, g_w) in fp32, None where `mask` = [input, weight, False] does not ask.
+    With bf16 operands the data gradient of a non-transposed layer comes from the library's forward kernels
+    (_dgrad_as_forward: rounded to nearest; DESIGN 3.7 has the times); a transposed layer's already does (its backward-data IS a
+    forward convolution), and every weight gradient is rounded to nearest as the library returns it."""
     if low is not None:
         g_r, x, w = g_r.to(low), x.to(low), w.to(low)
     nd = w.dim() - 2
-    g_x, g_w, _ = torch.ops.aten.convolution_backward(g_r, x, w, None, [stride] * nd, [padding] * nd, [1] * nd, transposed,
-                                                      [1 if transposed else 0] * nd, 1, mask)
+    as_fwd = low is not None and mask[0] and not transposed
+    lib = [mask[0] and not as_fwd, mask[1], False]
+    g_x = g_w = None
+    if lib[0] or lib[1]:
+        g_x, g_w, _ = torch.ops.aten.convolution_backward(g_r, x, w, None, [stride] * nd, [padding] * nd, [1] * nd, transposed,
+                                                          [1 if transposed else 0] * nd, 1, lib)
+    if as_fwd:
+        g_x = _dgrad_as_forward(g_r, w, stride, padding, x.shape[2:])
     return (g_x.float() if mask[0] else None), (g_w.float() if mask[1] else None)
 
 
@@ -578,7 +610,8 @@ class CostRegFn(Function):
     """CostRegNet under autograd with its FORWARD on the HIP kernels (csrc/costreg.hip, 1 ms instead of the library's
     8-11 ms): the raw output of every layer, its norm constants and batch moments are kept, and the backward pass
     walks the U-Net in reverse with the library's own convolution backward on them (aten.convolution_backward) and
-    zest_costreg_bn_bwd for norm + leaky ReLU; the skip additions are a few elementwise operations.
+    zest_costreg_bn_bwd for norm + leaky ReLU; the skip additions are a few elementwise operations.  With bf16 operands
+    the data gradients of the seven layers of the way down come from the library's forward kernels (_conv_bwd says why).
     Two opt-in arguments for layer 0, the one layer that reads the 41-channel cost volume at full resolution
     (_conv0_bwd); both hold for bf16 operands (passes == 1) only - with passes == 3 they change nothing:
     hip_wgrad (MVSNet.zest_hip_costreg_wgrad): the weight gradient comes from zest_costreg_wgrad

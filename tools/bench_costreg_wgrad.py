@@ -9,20 +9,18 @@
                library's data gradient alone (mask [True, False, False], an uninitialised bf16 tensor standing in for
                the cost volume), and the two launches of zest_costreg_wgrad on the channels-last fp32 tensors
 
-Both are warmed up; then they alternate in blocks of synchronised iterations (host clock around the call + device
-synchronise), so drift of the machine lands on both alike.  Device times per kernel come from torch.profiler in a pass of
-its own after the timing.  A gain is stated only where it exceeds the spread of the library's two measurements.
+Timed by the interleaved A/B protocol of tools/ab_timing.py; the profiler pass also yields the device time per kernel.
 
     python tools/bench_costreg_wgrad.py [--iters 40] [--out profiles/costreg_wgrad_128x120x176.json]
     python tools/bench_costreg_wgrad.py --loop 5       # both ways a few times, for a kernel-trace profiler run
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), ROOT):
@@ -38,14 +36,10 @@ LOW = torch.bfloat16
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=40, help="timed iterations per variant")
-    ap.add_argument("--block", type=int, default=10, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--loop", type=int, default=0, help="run both ways this many times and exit")
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=40, block=10, warmup=5)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_costreg_wgrad: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_costreg_wgrad")
     torch.backends.cudnn.benchmark = True
     gen = torch.Generator().manual_seed(0)
     cost = torch.randn(1, CIN, D, H, W, generator=gen).to(DEV)                       # as VolumeCostFn returns it
@@ -71,50 +65,27 @@ def main():
             library(), hip()
         torch.cuda.synchronize()
         return
-    for k in WAYS:
-        for _ in range(a.warmup):
-            steps[k]()
-    torch.cuda.synchronize()
+    step = lambda k: steps[k]()  # noqa: E731
+    ab_timing.warm_up(WAYS, step, a.warmup)
     (gx_a, gw_a), (gx_b, gw_b) = library(), hip()
     l2 = lambda p, q: float((p - q).norm() / q.norm())
     agree = dict(g_w_rel_l2=l2(gw_b, gw_a), g_x_rel_l2=l2(gx_b, gx_a))
     del gx_a, gx_b
-    total = {k: 0.0 for k in WAYS}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for k in WAYS:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                steps[k]()
-                torch.cuda.synchronize()
-            total[k] += time.perf_counter() - t0
-        done += n_it
-    ms = {k: 1e3 * total[k] / a.iters for k in WAYS}
+    ms = ab_timing.alternate(WAYS, step, a.iters, a.block)
     kernels = {}
     for k in WAYS[:2]:
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            steps[k]()
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-        kernels[k] = [dict(name=e.name[:96], us=round(e.device_time_total, 1)) for e in evs]
+        kernels[k] = [dict(name=e.name[:96], us=round(e.device_time_total, 1)) for e in ab_timing.profile_step(step, k)]
     ours_us = {n: sum(e["us"] for e in kernels["hip"] if n in e["name"] and (n != "wgrad_kernel" or "finish" not in e["name"])) for n in OURS}
-    spread = abs(ms["library"] - ms["library_again"])
-    gain = min(ms["library"], ms["library_again"]) - ms["hip"]
+    spread, gain, faster = ab_timing.spread_gain(ms, "library", "hip")
     upw, n_wg = zest_hip.costreg_wgrad_launch_shape(D, H, W)
     floor_us = (D * H * W * (48 + 8) * 4) / 8.0e12 * 1e6
     out = dict(bench="costreg_wgrad", volume=[D, H, W], cin=CIN, iters=a.iters, block=a.block, warmup=a.warmup,
                device=torch.cuda.get_device_name(0), ms_per_call={k: round(v, 4) for k, v in ms.items()},
                library_spread_ms=round(spread, 4), gain_over_library_ms=round(gain, 4),
-               hip_faster_than_library_by_more_than_spread=bool(gain > spread), device_us_of_the_new_kernels=ours_us,
+               hip_faster_than_library_by_more_than_spread=faster, device_us_of_the_new_kernels=ours_us,
                byte_floor_us_at_8TBps=round(floor_us, 1), launch=dict(units_per_wg=upw, n_wg=n_wg, work_mb=round(n_wg * 27 * 8 * 48 * 4 / 1e6, 1)),
                hip_against_library=agree, kernels_per_call=kernels)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(out, a.out)
 
 
 if __name__ == "__main__":

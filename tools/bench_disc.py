@@ -9,20 +9,18 @@ ndf 64), two legs, each two ways in one process:
             autograd; measured twice (.., *_torch_again) for the spread
   *_hip     zest_networks.GRAFDiscriminator on the kernels of csrc/disc.hip
 
-Every variant is warmed up, then the variants alternate in blocks of synchronised iterations (host clock around the step
-+ device synchronise), so drift of the machine lands on all of them alike.  Every variant restarts from the same u and v
-buffers each block.  The kernel count of one step comes from torch.profiler, in a pass of its own after the timing.  A
-gain is stated only where it exceeds the spread of the torch path it is measured against; no time is fixed in advance.
+Timed by the interleaved A/B protocol of tools/ab_timing.py; every variant restarts from the same u and v buffers each
+block.
 
     python tools/bench_disc.py [--iters 400] [--out profiles/disc_step_1x64.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests")):
@@ -37,15 +35,11 @@ DEV = "cuda:0"
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
     if a.iters < 200:
         ap.error("--iters must be at least 200")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_disc: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_disc")
     st = dc.state(IMSIZE, NDF, SEED)
     inp = {k: torch.from_numpy(v).to(DEV) for k, v in dc.patches(B, IMSIZE, SEED).items()}
     nets = dict(torch=dc.load(dc.Composition(3, NDF, IMSIZE), st, torch.float32, DEV).train(),
@@ -100,33 +94,13 @@ def main():
             num, den = num + float(((g - g0).double() ** 2).sum()), den + float((g0.double() ** 2).sum())
         rel_l2[leg] = (num / den) ** 0.5
         assert rel_l2[leg] <= 1e-3, (leg, rel_l2[leg])
-    for name in order:
-        for _ in range(a.warmup):
-            step(name)
-    torch.cuda.synchronize()
-    total = {n: 0.0 for n in order}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for name in order:
-            reset(nets[name.split("_")[1]])
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                step(name)
-                torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
-        done += n_it
-    ms = {n: 1e3 * total[n] / a.iters for n in order}
+    ab_timing.warm_up(order, step, a.warmup)
+    ms = ab_timing.alternate(order, step, a.iters, a.block, before_block=lambda name: reset(nets[name.split("_")[1]]))
     kernels = {}
     for name in order:
         if name.endswith("_again"):
             continue
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            step(name)
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and not e.name.startswith(("Memcpy", "Memset"))]
+        evs = ab_timing.profile_step(step, name)
         kernels[name] = len(evs)
         kernels[name + "_disc_hip"] = sum("_kernel" in e.name and any(k in e.name for k in (
             "sn_", "conv_fwd", "norm_finish", "last_fwd", "last_bwd", "norm_bwd", "plain_bwd", "dgrad", "wgrad")) for e in evs)
@@ -135,17 +109,11 @@ def main():
                gradient_elements_outside_tolerance=outside, gradient_relative_l2_error={k: float("%.3g" % v) for k, v in rel_l2.items()})
     faster = {}
     for leg in legs:
-        spread = abs(ms[leg + "_torch"] - ms[leg + "_torch_again"])
-        gain = min(ms[leg + "_torch"], ms[leg + "_torch_again"]) - ms[leg + "_hip"]
+        spread, gain, faster[leg] = ab_timing.spread_gain(ms, leg + "_torch", leg + "_hip")
         res[leg + "_torch_spread_ms"], res[leg + "_gain_ms"] = round(spread, 4), round(gain, 4)
-        faster[leg] = bool(gain > spread)
     res["hip_faster_than_torch_by_more_than_spread"] = faster
     res["device"] = torch.cuda.get_device_name(0)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -7,22 +7,21 @@ patch of 64 x 64 rays and its target, forward plus the gradient with respect to 
                measured twice (.., torch_again) for the spread
   hip          zest_losses.perceptual_loss on zest_networks.LPIPS, the kernels of csrc/lpips.hip
 
-Every variant is warmed up, then the variants alternate in blocks of synchronised iterations (host clock around the step
-+ device synchronise), so drift of the machine lands on all of them alike.  The kernel count of one step comes from
-torch.profiler, in a pass of its own after the timing.  A gain is stated only where it exceeds the spread of the two
-torch measurements; no time is fixed in advance.  --frame also times, once and forward only, the 288 x 512 frame of
-the validation metric (val_lpips), both ways; its throughput is not what the kernels were laid out for.
+Timed by the interleaved A/B protocol of tools/ab_timing.py.  --frame also times, once and forward only and one way after
+the other, the 288 x 512 frame of the validation metric (val_lpips), both ways; its throughput is not what the kernels
+were laid out for.
 
     python tools/bench_lpips.py [--iters 400] [--frame] [--out profiles/lpips_step_1x64.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests")):
@@ -39,16 +38,12 @@ OURS = ("pack_kernel", "conv1_kernel", "conv_kernel", "finish_kernel", "sum_kern
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--frame", action="store_true", help="also time the forward of one 288 x 512 frame, both ways")
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
     if a.iters < 200:
         ap.error("--iters must be at least 200")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_lpips: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_lpips")
     st = lc.state(SEED)
     nets = dict(torch=lc.load(lc.Composition(), st, torch.float32, DEV).eval(),
                 hip=lc.load(zest_networks.LPIPS(net='alex'), st, torch.float32, DEV).eval())
@@ -78,38 +73,19 @@ def main():
     rel_l2 = (float(((g - g0).double() ** 2).sum()) / float((g0.double() ** 2).sum())) ** 0.5
     assert rel_l2 <= 1e-3, rel_l2
 
-    for name in order:
-        for _ in range(a.warmup):
-            step(name.split("_")[0])
-    torch.cuda.synchronize()
-    total = {n: 0.0 for n in order}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for name in order:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                step(name.split("_")[0])
-                torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
-        done += n_it
-    ms = {n: 1e3 * total[n] / a.iters for n in order}
+    timed = lambda name: step(name.split("_")[0])  # noqa: E731
+    ab_timing.warm_up(order, timed, a.warmup)
+    ms = ab_timing.alternate(order, timed, a.iters, a.block)
     kernels = {}
     for name in ("torch", "hip"):
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            step(name)
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and not e.name.startswith(("Memcpy", "Memset"))]
+        evs = ab_timing.profile_step(step, name)
         kernels[name] = len(evs)
         kernels[name + "_lpips_hip"] = sum(any(k in e.name for k in OURS) for e in evs)
-    spread = abs(ms["torch"] - ms["torch_again"])
-    gain = min(ms["torch"], ms["torch_again"]) - ms["hip"]
+    spread, gain, faster = ab_timing.spread_gain(ms, "torch", "hip")
     res = dict(bench="lpips_step", patches=1, patch_size=PS, iters=a.iters, block=a.block, warmup=a.warmup,
                ms_per_step={k: round(v, 4) for k, v in ms.items()}, kernels_per_step=kernels,
                gradient_elements_outside_tolerance=outside, gradient_relative_l2_error=float("%.3g" % rel_l2),
-               torch_spread_ms=round(spread, 4), gain_ms=round(gain, 4), hip_faster_than_torch_by_more_than_spread=bool(gain > spread))
+               torch_spread_ms=round(spread, 4), gain_ms=round(gain, 4), hip_faster_than_torch_by_more_than_spread=faster)
     if a.frame:
         f0, f1 = (torch.from_numpy(x).to(DEV) for x in lc.images(1, FRAME[0], FRAME[1], SEED))
         frame_ms = {}
@@ -128,11 +104,7 @@ def main():
         assert abs(float(vals["hip"]) - float(vals["torch"])) <= 1e-3 * abs(float(vals["torch"]))
         res["frame_%dx%d_forward_ms" % FRAME] = frame_ms
     res["device"] = torch.cuda.get_device_name(0)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -9,10 +9,7 @@ ndf=64 GRAF discriminator, with fixed random gradients, three ways, each with an
   fused        torch.optim.Adam(fused=True), preceded by clip_grad_norm_ with the clip
   hip          zest_optim.Adam (csrc/optim.hip), the clip inside the step (max_grad_norm=1)
 
-Every variant owns a copy of the parameters and is warmed up; then the variants alternate in blocks of synchronised
-iterations (host clock around the call + device synchronise), so drift of the machine lands on all of them alike.  The
-kernel count of one call comes from torch.profiler, in a pass of its own after the timing.  A gain over the reference's
-composition is stated only where it exceeds the spread of its two measurements; no time is fixed in advance.
+Every variant owns a copy of the parameters; both legs are timed by the interleaved A/B protocol of tools/ab_timing.py.
 clip_grad_norm_ scales the gradients in place, so torch's gradients shrink to norm 1 in the first call and are multiplied
 by 1 from then on: the work per call does not change.
 
@@ -36,12 +33,12 @@ beyond the run).  The claim is whether generic - amp exceeds the spread of gener
     python tools/bench_optimizer.py --loop 200       # only zest_optim.Adam with the clip, for a kernel-trace profiler run
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests"), ROOT):
@@ -116,43 +113,25 @@ def build_amp(way, groups, seed):
 
 def amp_leg(a, groups):
     steps = {w: build_amp(w.split("_")[0], groups, 0) for w in AMP_WAYS}
-    for w in AMP_WAYS:
-        for _ in range(a.warmup):
-            steps[w]()
-    torch.cuda.synchronize()
-    total = {w: 0.0 for w in AMP_WAYS}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for w in AMP_WAYS:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                steps[w]()
-            torch.cuda.synchronize()                         # once per block: a synchronise inside a step costs its overlap
-            total[w] += time.perf_counter() - t0
-        done += n_it
-    ms = {w: 1e3 * total[w] / a.iters for w in AMP_WAYS}
-    spread = abs(ms["generic"] - ms["generic_again"])
-    gain = min(ms["generic"], ms["generic_again"]) - ms["amp"]
+    step = lambda w: steps[w]()  # noqa: E731
+    ab_timing.warm_up(AMP_WAYS, step, a.warmup)
+    # synchronised once per block: a synchronise inside a step costs its overlap
+    ms = ab_timing.alternate(AMP_WAYS, step, a.iters, a.block, sync_each_step=False)
+    spread, gain, faster = ab_timing.spread_gain(ms, "generic", "amp")
     shapes = groups[0] + groups[1]
     return dict(tensors=len(shapes), elements=sum(int(torch.Size(s).numel()) for s in shapes), scale=AMP_SCALE,
                 ms_per_iteration={k: round(v, 4) for k, v in ms.items()}, generic_spread_ms=round(spread, 4),
-                gain_over_generic_ms=round(gain, 4), amp_faster_than_generic_by_more_than_spread=bool(gain > spread),
+                gain_over_generic_ms=round(gain, 4), amp_faster_than_generic_by_more_than_spread=faster,
                 gain_over_fused_ms=round(ms["fused"] - ms["amp"], 4))
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--loop", type=int, default=0, help="run only zest_optim.Adam with the clip this many times on each set")
     ap.add_argument("--amp", action="store_true", help="the GradScaler leg on the generator's parameters instead")
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_optimizer: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_optimizer")
     sets = parameter_sets()
     if a.loop:
         for name, groups in sets.items():
@@ -166,11 +145,7 @@ def main():
     if a.amp:
         out = dict(bench="optimizer_step_amp", iters=a.iters, block=a.block, warmup=a.warmup, lr=LR, device=torch.cuda.get_device_name(0),
                    sets={"generator": amp_leg(a, sets["generator"])})
-        line = json.dumps(out)
-        print(line)
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write(line + "\n")
+        ab_timing.emit(out, a.out)
         return
     out = dict(bench="optimizer_step", iters=a.iters, block=a.block, warmup=a.warmup, lr=LR, device=torch.cuda.get_device_name(0), sets={})
     for name, groups in sets.items():
@@ -179,46 +154,23 @@ def main():
         res = dict(tensors=len(shapes), elements=elements)
         for clip in (True, False):
             steps = {w: build(w.split("_")[0], clip, groups, 0)[0] for w in WAYS}
-            for w in WAYS:
-                for _ in range(a.warmup):
-                    steps[w]()
-            torch.cuda.synchronize()
-            total = {w: 0.0 for w in WAYS}
-            done = 0
-            while done < a.iters:
-                n_it = min(a.block, a.iters - done)
-                for w in WAYS:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    for _ in range(n_it):
-                        steps[w]()
-                        torch.cuda.synchronize()
-                    total[w] += time.perf_counter() - t0
-                done += n_it
-            ms = {w: 1e3 * total[w] / a.iters for w in WAYS}
+            step = lambda w: steps[w]()  # noqa: E731
+            ab_timing.warm_up(WAYS, step, a.warmup)
+            ms = ab_timing.alternate(WAYS, step, a.iters, a.block)
             kernels = {}
             for w in WAYS[:3]:
-                with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-                    steps[w]()
-                    torch.cuda.synchronize()
-                evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-                       and not e.name.startswith(("Memcpy", "Memset", "Optimizer."))]    # the last: step's profiler range
+                evs = ab_timing.profile_step(step, w, skip=("Memcpy", "Memset", "Optimizer."))    # the last: step's profiler range
                 kernels[w] = len(evs)
                 if w == "hip":
                     kernels["hip_optim_hip"] = sum(any(k in e.name for k in OURS) for e in evs)
                     kernels["hip_others"] = sorted(e.name[:80] for e in evs if not any(k in e.name for k in OURS))
-            spread = abs(ms["torch"] - ms["torch_again"])
-            gain = min(ms["torch"], ms["torch_again"]) - ms["hip"]
+            spread, gain, faster = ab_timing.spread_gain(ms, "torch", "hip")
             res["clip_1" if clip else "no_clip"] = dict(
                 ms_per_call={k: round(v, 4) for k, v in ms.items()}, kernels_per_call=kernels, torch_spread_ms=round(spread, 4),
-                gain_over_torch_ms=round(gain, 4), hip_faster_than_torch_by_more_than_spread=bool(gain > spread),
+                gain_over_torch_ms=round(gain, 4), hip_faster_than_torch_by_more_than_spread=faster,
                 gain_over_fused_ms=round(ms["fused"] - ms["hip"], 4))
         out["sets"][name] = res
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(out, a.out)
 
 
 if __name__ == "__main__":

@@ -7,20 +7,17 @@ rays), two ways in one process:
                   the reference) with autograd; measured twice (.., patch_torch_again) for the spread
   patch_hip       zest_losses.patch_terms: two HIP launches
 
-Every variant is warmed up, then the variants alternate in blocks of synchronised iterations (host clock around forward +
-backward + device synchronise), so drift of the machine lands on all of them alike.  The kernel count of one step comes
-from torch.profiler, in a pass of its own after the timing.  A gain is stated only where it exceeds the spread of the
-torch path it is measured against.
+Timed by the interleaved A/B protocol of tools/ab_timing.py; one step is forward + backward.
 
     python tools/bench_patch_terms.py [--patches 1] [--patch-size 64] [--iters 400] [--out profiles/patch_terms_1x64.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests")):
@@ -35,15 +32,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--patches", type=int, default=1)
     ap.add_argument("--patch-size", type=int, default=64)
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
     if a.iters < 200:
         ap.error("--iters must be at least 200")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_patch_terms: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_patch_terms")
     hp = pc.CONFIGS[CONFIG]["hparams"]
     w = dict(mse=1.0, tv=hp["lambda_depth_reg"] ** 2, smooth=hp["lambda_depth_smooth"] ** 2)
     ps = a.patch_size
@@ -76,45 +69,21 @@ def main():
     for g, g0 in zip(check["patch_hip"][1], check["patch_torch"][1]):
         outside += int(((g - g0).abs() > 1e-4 * g0.abs().max() + 1e-3 * g0.abs()).sum())
     assert outside == 0, outside                                # the recipe keeps every |.| away from 0: no element is excused
-    for name in order:
-        for _ in range(a.warmup):
-            step(name)
-    torch.cuda.synchronize()
-    total = {n: 0.0 for n in order}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for name in order:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                step(name)
-                torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
-        done += n_it
-    ms = {n: 1e3 * total[n] / a.iters for n in order}
+    ab_timing.warm_up(order, step, a.warmup)
+    ms = ab_timing.alternate(order, step, a.iters, a.block)
     kernels = {}
     for name in variants:
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            step(name)
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and not e.name.startswith(("Memcpy", "Memset"))]
+        evs = ab_timing.profile_step(step, name)
         kernels[name] = len(evs)
         kernels[name + "_hip"] = sum("patch_terms_" in e.name for e in evs)
-    spread = abs(ms["patch_torch"] - ms["patch_torch_again"])
-    gain = min(ms["patch_torch"], ms["patch_torch_again"]) - ms["patch_hip"]
+    spread, gain, faster = ab_timing.spread_gain(ms, "patch_torch", "patch_hip")
     res = dict(bench="patch_terms", patches=a.patches, patch_size=ps, rays=a.patches * ps * ps, config=CONFIG, weights=w,
                iters=a.iters, block=a.block, warmup=a.warmup, ms_per_step={k: round(v, 4) for k, v in ms.items()},
                torch_spread_ms=round(spread, 4), gain_ms=round(gain, 4), kernels_per_step=kernels,
                gradient_elements_outside_tolerance=outside,
-               patch_hip_faster_than_torch_by_more_than_spread=bool(gain > spread),
+               patch_hip_faster_than_torch_by_more_than_spread=faster,
                device=torch.cuda.get_device_name(0))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(res, a.out)
 
 
 if __name__ == "__main__":

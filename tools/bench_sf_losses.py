@@ -8,19 +8,17 @@ backward, at the workload's size (1024 rays x 128 samples), three ways in one pr
   per_name   zest_losses.compute_sf_smooth_loss x 2 + compute_sf_lke_loss x 2: four HIP launches
   fused      zest_losses.scene_flow_regularisers: one HIP launch
 
-Every variant is warmed up, then the variants alternate in blocks of synchronised iterations (host clock around
-forward + backward + device synchronise), so drift of the machine lands on all of them alike.  The kernel count of one
-step comes from torch.profiler, in a pass of its own after the timing.
+Timed by the interleaved A/B protocol of tools/ab_timing.py; one step is forward + backward.
 
     python tools/bench_sf_losses.py [--rays 1024] [--samples 128] [--iters 400] [--out profiles/sf_losses_1024x128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests")):
@@ -35,16 +33,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--samples", type=int, default=128)
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--chain-fwd", action="store_true")
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
     if a.iters < 200:
         ap.error("--iters must be at least 200")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_sf_losses: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_sf_losses")
     dev = "cuda:0"
     chain_bwd = not a.chain_fwd
     inp = sc.inputs(sc.SEED, a.rays, a.samples)
@@ -82,43 +76,20 @@ def main():
         off = sum(int(((g - g0).abs() > 1e-4 * g0.abs().max() + 1e-3 * g0.abs()).sum()) for g, g0 in zip(check[name][1], check["torch"][1]))
         outside[name] = off
         assert off <= 1e-5 * 4 * check["torch"][1][0].numel(), (name, off)
-    for name in order:
-        for _ in range(a.warmup):
-            step(name)
-    torch.cuda.synchronize()
-    total = {n: 0.0 for n in order}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for name in order:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                step(name)
-                torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
-        done += n_it
-    ms = {n: 1e3 * total[n] / a.iters for n in order}
+    ab_timing.warm_up(order, step, a.warmup)
+    ms = ab_timing.alternate(order, step, a.iters, a.block)
     kernels = {}
     for name in ("torch", "per_name", "fused"):
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            step(name)
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and not e.name.startswith(("Memcpy", "Memset"))]
+        evs = ab_timing.profile_step(step, name)
         kernels[name] = len(evs)
         kernels[name + "_hip"] = sum("sf_reg_kernel" in e.name for e in evs)
-    spread = abs(ms["torch"] - ms["torch_again"])
+    spread, _, faster = ab_timing.spread_gain(ms, "torch", "fused")
     res = dict(bench="sf_losses", rays=a.rays, samples=a.samples, chain_bwd=chain_bwd, iters=a.iters, block=a.block,
                warmup=a.warmup, ms_per_step={k: round(v, 4) for k, v in ms.items()}, torch_spread_ms=round(spread, 4),
                kernels_per_step=kernels, gradient_elements_outside_tolerance=outside,
-               fused_faster_than_torch_by_more_than_spread=bool(min(ms["torch"], ms["torch_again"]) - ms["fused"] > spread),
+               fused_faster_than_torch_by_more_than_spread=faster,
                device=torch.cuda.get_device_name(0))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -9,20 +9,18 @@
   step_torch      the whole step as a torch composition (the same restatement), with autograd
   step_hip        zest_losses.train_sf_step_loss
 
-Every variant is warmed up, then the variants alternate in blocks of synchronised iterations (host clock around forward +
-backward + device synchronise), so drift of the machine lands on all of them alike.  The kernel count of one step comes
-from torch.profiler, in a pass of its own after the timing.
+Timed by the interleaved A/B protocol of tools/ab_timing.py; one step is forward + backward.
 
     python tools/bench_sf_step_loss.py [--rays 1024] [--samples 128] [--iters 400] [--out profiles/sf_step_loss_1024x128.json]
 """
 import argparse
-import json
 import os
 import sys
-import time
 import types
 
 import torch
+
+import ab_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "zest-nerf_amd"), os.path.join(ROOT, "tests")):
@@ -37,15 +35,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--samples", type=int, default=128)
-    ap.add_argument("--iters", type=int, default=400, help="timed iterations per variant (at least 200)")
-    ap.add_argument("--block", type=int, default=50, help="iterations of one variant before the next takes over")
-    ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--out", default=None)
+    ab_timing.add_arguments(ap, iters=400, block=50, warmup=30)
     a = ap.parse_args()
     if a.iters < 200:
         ap.error("--iters must be at least 200")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_sf_step_loss: no HIP device (there is no CPU path to time)")
+    ab_timing.require_device("bench_sf_step_loss")
     cfg = ss.CONFIGS[CONFIG]
     hp = cfg["hparams"]
     r, cams = ss.leaves(ss.inputs(ss.SEED, a.rays, a.samples), torch.float32, "cuda:0", cfg["chain_bwd"], cfg["chain_5frames"])
@@ -93,46 +87,24 @@ def main():
                 n += g0.numel()
         outside[name] = off
         assert off <= 1e-5 * n, (name, off, n)
-    for name in order:
-        for _ in range(a.warmup):
-            step(name)
-    torch.cuda.synchronize()
-    total = {n: 0.0 for n in order}
-    done = 0
-    while done < a.iters:
-        n_it = min(a.block, a.iters - done)
-        for name in order:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(n_it):
-                step(name)
-                torch.cuda.synchronize()
-            total[name] += time.perf_counter() - t0
-        done += n_it
-    ms = {n: 1e3 * total[n] / a.iters for n in order}
+    ab_timing.warm_up(order, step, a.warmup)
+    ms = ab_timing.alternate(order, step, a.iters, a.block)
     kernels = {}
     for name in variants:
-        with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU, torch.profiler.ProfilerActivity.CUDA]) as prof:
-            step(name)
-            torch.cuda.synchronize()
-        evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
-               and not e.name.startswith(("Memcpy", "Memset"))]
+        evs = ab_timing.profile_step(step, name)
         kernels[name] = len(evs)
         kernels[name + "_hip"] = sum(any(k in e.name for k in ("sf_sample_", "sf_reg_kernel", "project_rays")) for e in evs)
-    spread = {b: abs(ms[b] - ms[b + "_again"]) for b in ("samples_torch", "step_torch")}
-    gain = {h: min(ms[b], ms[b + "_again"]) - ms[h] for h, b in (("samples_hip", "samples_torch"), ("step_hip", "step_torch"))}
+    spread, faster = {}, {}
+    for b, h in (("samples_torch", "samples_hip"), ("step_torch", "step_hip")):
+        spread[b], _, faster[h] = ab_timing.spread_gain(ms, b, h)
     res = dict(bench="sf_step_loss", rays=a.rays, samples=a.samples, config=CONFIG, iters=a.iters, block=a.block,
                warmup=a.warmup, ms_per_step={k: round(v, 4) for k, v in ms.items()},
                torch_spread_ms={k: round(v, 4) for k, v in spread.items()}, kernels_per_step=kernels,
                gradient_elements_outside_tolerance=outside,
-               samples_hip_faster_than_torch_by_more_than_spread=bool(gain["samples_hip"] > spread["samples_torch"]),
-               step_hip_faster_than_torch_by_more_than_spread=bool(gain["step_hip"] > spread["step_torch"]),
+               samples_hip_faster_than_torch_by_more_than_spread=faster["samples_hip"],
+               step_hip_faster_than_torch_by_more_than_spread=faster["step_hip"],
                device=torch.cuda.get_device_name(0))
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
+    ab_timing.emit(res, a.out)
 
 
 if __name__ == "__main__":

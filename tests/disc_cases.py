@@ -26,6 +26,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+import judges
+from judges import ATOL, RTOL
+
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MARGIN = 10.0
 INDICES = {32: (0, 3, 6, 9), 64: (0, 2, 5, 8, 11), 128: (0, 2, 5, 8, 11, 14)}
@@ -227,3 +230,29 @@ def load_fixture(B, imsize, ndf):
     names of run_steps, and `seed`."""
     with np.load(fixture_path(B, imsize, ndf), allow_pickle=False) as f:
         return {k: f[k] for k in f.files}
+
+
+# ------------------------------------------------------------------------------------------------ the judge
+def compare(got, want, imsize, ndf, name, digests=False):
+    """A dict of run_steps against the fixture's or the restatement's: gradients within ATOL max|want| + RTOL |want| per
+    element (at the digest shapes the generator's by relative L2 <= RTOL, the weights' norms and inner products with
+    the seeded directions within RTOL |g| (|d|)), everything else within ATOL + RTOL |want|."""
+    assert sorted(got) == sorted(k for k in want if k != "seed")
+    for k, v in got.items():
+        w, tag = np.asarray(want[k], np.float64), "%s: %s" % (name, k)
+        if k == "gen__grad__rgb" and digests:
+            judges.l2_close(v, w, tag, RTOL)
+        elif k == "gen__grad__rgb" or k.startswith("disc__grad__"):
+            judges.scaled_close(v, w, tag, ATOL, RTOL, nonzero=True)
+        elif k.startswith("disc__grad_norm__"):
+            assert np.isfinite(v) and np.isfinite(w), (tag, v, w)
+            assert abs(v - w) <= RTOL * w, (tag, v, w)
+        elif k.startswith("disc__grad_dots__"):
+            i = int(k.rsplit("__", 1)[1])
+            shape = state(imsize, ndf, 0)["main.%d.weight_orig" % i].shape
+            d_norm = np.linalg.norm(directions(imsize, ndf, i, shape).reshape(N_DIRS, -1), axis=1)
+            bound = RTOL * np.asarray(want["disc__grad_norm__%d" % i], np.float64) * d_norm
+            assert np.isfinite(v).all() and np.isfinite(w).all() and np.isfinite(bound).all(), (tag, v, w, bound)
+            assert not (~(np.abs(v - w) <= bound)).any(), (tag, v, w, bound)
+        else:
+            judges.close(np.atleast_1d(v), np.atleast_1d(w), name=tag)

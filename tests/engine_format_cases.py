@@ -40,16 +40,14 @@ import torch.nn.functional as F
 
 import golden_cases as gc
 import oracle_run as orun
+from gpu_cases import MAP_KEYS, TOL16
+from judges import ATOL, RTOL
 import zest_synth as zs
 from oracle import zest_oracle as zo
 
 F16_MAX = 65504.0
 ACCS32 = ("f32", "chunk32", "chunk32_rev")
 LEGACY = {"bf16": 3e-2, "f16": 4e-3}                       # test_mlp_bf16 / test_mlp_fp16: x scale + x |ref|
-TOL16 = {"bf16": (2e-2, 6e-2), "f16": (3e-3, 1e-2)}        # tests/test_hip_precision.py (colours, depths)
-MAP_KEYS = ("rgb_map", "depth_map", "rgb_map_ref", "depth_map_ref", "rgb_map_ref_dy", "depth_map_ref_dy",
-            "weights_map_dd")
-ATOL, RTOL = 1e-4, 1e-3                                    # the project's fp32-class tolerance
 FLIP_FLOOR, FLIP_CAP_MAX, RESTATED_SHARE_MAX, ORDER_FACTOR = 0.005, 0.10, 0.025, 4.0
 SPREAD_FLOOR = 0.005                                     # a scene's bound on a map is at least this share of TOL16
 

@@ -8,7 +8,7 @@ Reference: the oracle (oracle/zest_oracle.py) evaluated in float64 on the same f
 where the oracle has none (the `lindisp` depth, weighted_complement_sum, the inverse CDF).  Every `*_ref` takes the dtype:
 float64 for the comparison, float32 for the spread below and for the CPU guard.
 
-Rule (`tight`): every element within BASELINE.json's 1e-4 + 1e-3 |want| through test_hip_ops.close, which fails on a
+Rule (`tight`): every element within BASELINE.json's 1e-4 + 1e-3 |want| through judges.close, which fails on a
 one-sided NaN or infinity; and per output tensor  max|got - want64| <= F spread + 4 2^-24 max|want64|,  where
 spread = max|oracle_fp32 - oracle_fp64| of that tensor for that case: the error an fp32 evaluation of the same formula makes
 on these inputs.  It depends on the reference only.  F = 8 allows for another summation order and the device's expf / sincos
@@ -23,13 +23,13 @@ import torch
 
 import golden_cases as gc
 import grad_edge_cases as ge
+from judges import close, f64 as _np
 from oracle import zest_oracle as zo
-from test_hip_ops import close
 
 F64, F32 = torch.float64, torch.float32
 U24 = 2.0 ** -24
 F_DEFAULT = 8.0
-_t, _np = ge._t, ge._np
+_t = ge._t
 
 
 # ------------------------------------------------------------------------------ the rule

@@ -8,7 +8,7 @@ Reference: always the oracle (oracle/zest_oracle.py) under autograd on the same 
 takes the dtype to evaluate in - float64 for the comparison, float32 only for the CPU guard, which checks that the
 oracle's own fp32 evaluation passes the rule the kernels are held to.
 
-Rule (`rows_close`): |got - want| <= 1e-3 max_row|want| + 1e-3 |want|, the bound of test_hip_backward.gclose with the
+Rule (`rows_close`): |got - want| <= 1e-3 max_row|want| + 1e-3 |want|, the bound of backward_cases.gclose with the
 scale taken per row (one ray's block, one sample's 3-vector, one MLP input row); a row whose reference is entirely
 zero must be exactly zero.  Tensors accumulated in an order the reference does not share (the scattered volume
 gradient, the MLP parameter gradients) keep the per-tensor scale (`tensor_close`)."""
@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 import golden_cases as gc
+import judges
 import oracle_run
 from oracle import zest_oracle as zo
 
@@ -25,44 +26,9 @@ REL = 1e-3
 F64 = torch.float64
 
 
-# ------------------------------------------------------------------------------ the rule
-def _np(a):
-    return a.detach().double().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
-
-
-def rows_close(got, want, lead, name):
-    """got, want: arrays whose first `lead` axes index the rows.  -> the worst |got - want| / max_row|want|."""
-    got, want = _np(got), _np(want)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert np.isfinite(got).all(), "%s: non-finite entries" % name
-    assert np.isfinite(want).all(), "%s: the reference holds non-finite entries" % name
-    nrow = int(np.prod(want.shape[:lead], dtype=np.int64))
-    g, w = got.reshape(nrow, -1), want.reshape(nrow, -1)
-    scale = np.abs(w).max(1, keepdims=True)
-    err = np.abs(g - w)
-    dead = scale[:, 0] == 0
-    assert (g[dead] == 0).all(), "%s: %d rows with an all-zero reference are not exactly zero" % (name, (g[dead] != 0).any(1).sum())
-    bad = ~(err <= REL * scale + REL * np.abs(w))
-    frac = float((err[~dead] / scale[~dead]).max()) if (~dead).any() else 0.0
-    assert not bad.any(), "%s: %d/%d outside tolerance in %d rows, worst err / row max %.3g" % (
-        name, bad.sum(), bad.size, bad.any(1).sum(), frac)
-    return frac
-
-
-def tensor_close(got, want, name, exact_zeros=False):
-    """test_hip_backward.gclose, returning the worst |got - want| / max|want|.  exact_zeros: where the reference is
-    exactly zero (a voxel no sample touches) the result must be exactly zero."""
-    got, want = _np(got), _np(want)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert np.isfinite(got).all(), "%s: non-finite entries" % name
-    assert np.isfinite(want).all(), "%s: the reference holds non-finite entries" % name
-    scale = np.abs(want).max() + 1e-12
-    err = np.abs(got - want)
-    bad = ~(err <= REL * scale + REL * np.abs(want))
-    assert not bad.any(), "%s: %d/%d outside tolerance, max err %.3g (scale %.3g)" % (name, bad.sum(), bad.size, err.max(), scale)
-    if exact_zeros:
-        assert (got[want == 0] == 0).all(), "%s: entries with a zero reference are not exactly zero" % name
-    return float(err.max() / scale)
+# ------------------------------------------------------------------------------ the rule, at this family's tolerance
+rows_close = functools.partial(judges.rows_close, rel=REL)                                    # (got, want, lead, name)
+tensor_close = functools.partial(judges.scaled_close, atol=REL, rtol=REL, floor=1e-12)       # (got, want, name, exact_zeros=False)
 
 
 def _t(a, dtype):

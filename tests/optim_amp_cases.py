@@ -63,3 +63,10 @@ def adam64(p, m, v, g, t, lr, coef, betas=oc.BETAS, eps=oc.EPS, mutation=None):
     v64 = b2 * v + (1.0 - b2) * (g * g) * coef
     u = (m64 / (1.0 - b1 ** t)) / (np.sqrt(v64) / np.sqrt(1.0 - b2 ** t) + eps)
     return p - lr * u, m64, v64
+
+
+def judge(world, proto_t, old, got, flat, lr_of, coef, absent=(), label=""):
+    t = np.repeat(np.asarray(proto_t, dtype=np.float64), world.ns)
+    lr = np.repeat(np.asarray(lr_of, dtype=np.float64), world.ns)
+    present = ~np.isin(world.tensor_of, list(absent))
+    return oc.judge(got, old, flat, np.maximum(t, 1.0), lr, coef=coef, where=present, label=label)

@@ -17,6 +17,9 @@ Inputs: parameters uniform in [-1, 1]; gradient magnitudes log-uniform in [1e-6,
 element of the flat gradient exactly zero (there the update must be exactly zero at step 1); lr 5e-4, the reference's.
 """
 import numpy as np
+import torch
+
+from gpu_cases import DEV
 
 LR = 5e-4
 BETAS = (0.9, 0.999)
@@ -85,3 +88,114 @@ def norm64(grads):
 
 def coef64(norm, max_norm):
     return min(1.0, max_norm / (norm + 1e-6))
+
+
+# ------------------------------------------------------------------------------------------------ the tensors of the GPU tests
+SENTINEL = -7.25
+GUARD = 8
+
+
+class World:
+    """Parameters (and, with arena_state, their exp_avg / exp_avg_sq) as slices of sentinel-filled buffers.
+    specs: [(elements, offset of p past a 16-byte boundary in elements, the same of m, of v, group index)]."""
+
+    def __init__(self, specs, seed, arena_state=True):
+        self.ns = [s[0] for s in specs]
+        self.groups = [s[4] for s in specs]
+        self.total = sum(self.ns)
+        self.bounds = np.concatenate([[0], np.cumsum(self.ns)]).astype(np.int64)
+        self.tensor_of = np.repeat(np.arange(len(specs)), self.ns)
+        values = parameters(seed, self.total)
+        self.arenas, self.inside, self.slices = [], [], []
+        for which in range(3 if arena_state else 1):
+            cur, starts = 64, []
+            for s in specs:
+                cur = (cur + 3) // 4 * 4 + s[1 + which]
+                starts.append(cur)
+                cur += s[0] + GUARD
+            host = np.full(cur + 64, SENTINEL, dtype=np.float32)
+            inside = np.zeros(cur + 64, dtype=bool)
+            for k, (a, n) in enumerate(zip(starts, self.ns)):
+                host[a:a + n] = values[self.bounds[k]:self.bounds[k + 1]] if which == 0 else 0.0
+                inside[a:a + n] = True
+            arena = torch.from_numpy(host).to(DEV)
+            assert arena.data_ptr() % 16 == 0
+            self.arenas.append(arena), self.inside.append(inside)
+            self.slices.append([arena[a:a + n] for a, n in zip(starts, self.ns)])
+        self.ps = [torch.nn.Parameter(t) for t in self.slices[0]]
+        self.t = [0] * len(specs)
+
+    def optimizer(self, cls, lr=LR, **kw):
+        n_groups = max(self.groups) + 1
+        groups = [{"params": [p for p, g in zip(self.ps, self.groups) if g == k], "lr": lr * 10 ** k} for k in range(n_groups)]
+        opt = cls(groups, lr=lr, betas=BETAS, eps=EPS, **kw)
+        if len(self.arenas) == 3:                            # the state tensors inside their own sentinel buffers
+            for p, m, v in zip(self.ps, self.slices[1], self.slices[2]):
+                opt.state[p] = {"step": torch.tensor(0.0, dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+        return opt
+
+    def read(self, opt):
+        """-> (p, m, v) of all tensors, flat, as float32 numpy arrays (zeros for a state that does not exist yet)."""
+        def cat(ts):
+            return torch.cat([t.detach().reshape(-1) for t in ts]).cpu().numpy() if ts else np.zeros(0, dtype=np.float32)
+        m = [opt.state[p]["exp_avg"] if "exp_avg" in opt.state.get(p, {}) else torch.zeros_like(p) for p in self.ps]
+        v = [opt.state[p]["exp_avg_sq"] if "exp_avg_sq" in opt.state.get(p, {}) else torch.zeros_like(p) for p in self.ps]
+        return cat(self.ps), cat(m), cat(v)
+
+    def set_grads(self, flat, absent=(), views=()):
+        """p.grad = a fresh device tensor per parameter (None for `absent`; for `views` a slice that starts 4 bytes past
+        a 16-byte boundary) -> the gradients as set, for the bit-for-bit comparison afterwards."""
+        dev = torch.from_numpy(flat).to(DEV)
+        kept = []
+        for k, p in enumerate(self.ps):
+            if k in absent:
+                p.grad = None
+                kept.append(None)
+                continue
+            g = dev[self.bounds[k]:self.bounds[k + 1]]
+            if k in views:
+                tmp = torch.empty(self.ns[k] + 1, device=DEV)
+                tmp[1:] = g
+                p.grad = tmp[1:]
+                assert p.grad.data_ptr() % 16 == 4 and p.grad.is_contiguous()
+            else:
+                p.grad = g.clone()
+            kept.append(p.grad.clone())
+        return kept
+
+    def check_sentinels(self):
+        for arena, inside in zip(self.arenas, self.inside):
+            outside = arena.cpu().numpy()[~inside]
+            assert (outside == SENTINEL).all(), "%d elements outside the tensors were written" % int((outside != SENTINEL).sum())
+
+    def step(self, opt, flat, absent=(), views=(), coef=1.0, judged=True, where=None, label=""):
+        """One step, judged unless told otherwise -> (state before, state after, worst error / bound)."""
+        lr_of = [opt.param_groups[g]["lr"] for g in self.groups]
+        old = self.read(opt)
+        kept = self.set_grads(flat, absent, views)
+        opt.step()
+        got = self.read(opt)
+        for k in range(len(self.ps)):
+            if k not in absent:
+                self.t[k] += 1
+                assert torch.equal(self.ps[k].grad.view(torch.int32), kept[k].view(torch.int32)), "a gradient was written"
+        present = ~np.isin(self.tensor_of, list(absent))
+        worst = None
+        if judged:
+            t = np.repeat(np.asarray(self.t, dtype=np.float64), self.ns)
+            lr = np.repeat(np.asarray(lr_of, dtype=np.float64), self.ns)
+            mask = present if where is None else present & where
+            worst = judge(got, old, flat, np.maximum(t, 1.0), lr, coef=coef, where=mask, label=label)
+        for a, b in zip(old, got):                           # a skipped parameter: p, m, v bit for bit
+            assert np.array_equal(a[~present], b[~present])
+        if len(self.arenas) == 3:
+            self.check_sentinels()
+        return old, got, worst
+
+
+def _specs(sizes, groups=2, misaligned=()):
+    specs = [(n, 0, 0, 0, k % groups) for k, n in enumerate(sizes)]
+    return specs + [(n, a, b, c, (len(specs) + k) % groups) for k, (n, a, b, c) in enumerate(misaligned)]
+
+
+MISALIGNED = ((4099, 1, 0, 0), (37, 3, 2, 1))                # Parameters over buf[1:] and buf[3:]; their state here and there

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 import sf_loss_cases as sc
+from judges import scaled_close, ATOL, RTOL
 
 GOLDEN_DIR = sc.GOLDEN_DIR
 H, W = sc.H, sc.W
@@ -260,3 +261,33 @@ def load_fixture(R, S):
     term's lambda at 1 and every other lambda at 0, on each tensor the term reads."""
     with np.load(fixture_path(R, S), allow_pickle=False) as f:
         return {k: f[k] for k in f.files}
+
+
+def cpu_results(R=4, S=10):
+    """An all-zero result dict of the scene-flow step on the CPU: what the wrappers must refuse before the library."""
+    r = {k: torch.zeros(1, R, S, 3) for k in SF + PTS}
+    r.update({k: torch.zeros(1, R, S) for k in PROB + ("weights_ref_dy", "raw_blend_w")})
+    r.update({k: torch.zeros(1, R, 3) for k in RGB + ("target_s",)})
+    r.update({k: torch.zeros(1, R, 2) for k in ("rays_flow_fwd_gt", "rays_flow_bwd_gt")})
+    r.update({k: torch.zeros(1, R) for k in ("prob_map_post", "prob_map_prev", "weights_map_dd", "rays_mask_fwd_gt",
+                                             "rays_mask_bwd_gt", "depth_map_ref_dy", "depth_gt")})
+    r["chain_bwd"], r["chain_5frames"] = True, True
+    return r
+
+
+def close_grads(p, want, name, keys=None):
+    """The gradients of the leaves p[k] (all of them, or `keys`; a leaf that is None is not an argument of the call)
+    against want[k] within ATOL max|want| + RTOL |want|: none where none was asked for, exact zeros for a zero reference."""
+    for k in p if keys is None else keys:
+        leaf = p[k]
+        if leaf is None:
+            continue
+        if not leaf.requires_grad:
+            assert leaf.grad is None, (name, k)
+            continue
+        w = want[k]
+        assert leaf.grad is not None and leaf.grad.shape == leaf.shape and leaf.grad.dtype == leaf.dtype, (name, k)
+        if not np.abs(w).max() > 0:
+            assert (leaf.grad == 0).all(), (name, k)
+            continue
+        scaled_close(leaf.grad.reshape(w.shape), w, "%s: d / d %s" % (name, k), ATOL, RTOL)

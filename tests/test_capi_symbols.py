@@ -1,18 +1,13 @@
 """CPU: the C-ABI library loads and exports every symbol include/zest_render.h declares."""
 import ctypes
 import os
-import re
 import sys
 
 import pytest
 
+from package_cases import _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    src = open(os.path.join(ROOT, "include", "zest_render.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(zest_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_header_and_binding_agree():

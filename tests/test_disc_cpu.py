@@ -11,15 +11,9 @@ import torch
 
 import disc_cases as dc
 import patch_cases as pc
+from judges import finite_close
 
 ATOL, RTOL = 2e-6, 2e-5                                   # test_oracle_golden.py
-
-
-def _close(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    err = np.abs(got - want)
-    assert (err <= ATOL + RTOL * np.abs(want)).all(), (name, err.max(), np.abs(want).max())
 
 
 @pytest.mark.parametrize("case", dc.CASES, ids=lambda c: "%dx%d_ndf%d" % c)
@@ -32,7 +26,7 @@ def test_composition_reproduces_the_reference(case):
                        digests=case in dc.DIGEST_CASES)
     assert sorted(got) == sorted(k for k in fx if k != "seed")
     for k, v in got.items():
-        _close(v, fx[k], "%s: %s" % (case, k))
+        finite_close(v, fx[k], "%s: %s" % (case, k), ATOL, RTOL)
 
 
 def test_fixtures_hold_what_the_tests_read():

@@ -8,96 +8,11 @@ import importlib
 import os
 import subprocess
 import sys
-import textwrap
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "zest-nerf_amd")
-
-STANDINS = {
-    "utils.py": """
-        def visualize_depth(depth, minmax=None): return "caller.visualize_depth"
-        def NDC2Euclidean(xyz_ndc, H, W, f): return "caller.NDC2Euclidean"
-        def build_rays(*a, **k): return "caller.build_rays"
-        def build_rays_dy(*a, **k): return "caller.build_rays_dy"
-        def homo_warp(*a, **k): return "caller.homo_warp"
-        def index_point_feature(*a, **k): return "caller.index_point_feature"
-        def build_color_volume(*a, **k): return "caller.build_color_volume"
-        def projection_from_ndc(*a, **k): return "caller.projection_from_ndc"
-    """,
-    "renderer.py": """
-        from utils import index_point_feature, build_color_volume
-        def rendering(*a, **k): return "caller.rendering"
-        def raw2outputs(*a, **k): return "caller.raw2outputs"
-    """,
-    "networks.py": """
-        from inplace_abn import InPlaceABN
-        from utils import homo_warp, build_rays, build_rays_dy
-        from renderer import rendering
-        class Embedding: pass
-        class MVSNeRF: pass
-        class MVSNet:
-            norm = InPlaceABN
-        class MVSNeRF_G: pass
-        class DyMVSNeRF_G: pass
-        class BasicDiscriminator: marker = "caller"
-        class NLayerDiscriminator: marker = "caller"
-        class PixelDiscriminator: marker = "caller"
-        class GRAFDiscriminator: marker = "caller"
-        def feat2viz(*a): return "caller.feat2viz"
-    """,
-    "losses.py": """
-        from utils import NDC2Euclidean
-        def total_variation_loss(*a): return "caller.tv"
-        def get_disparity_smoothness(*a): return "caller.smooth"
-        def distortion_loss(*a): return "caller.distortion"
-        def mse_masked(*a): return "caller.mse"
-        def mae_masked(*a): return "caller.mae"
-        def compute_depth_loss(*a): return "caller.depth"
-        def compute_sf_smooth_loss(*a): return "caller.sf_smooth"
-        def compute_sf_lke_loss(*a): return "caller.sf_lke"
-    """,
-    # the reference's own import lines for the path (train.py:36-44), then what a script does with them
-    "train_imports.py": """
-        from networks import Embedding, MVSNeRF, MVSNet, MVSNeRF_G, DyMVSNeRF_G, \\
-            BasicDiscriminator, NLayerDiscriminator, PixelDiscriminator, GRAFDiscriminator
-        from utils import build_rays, visualize_depth, projection_from_ndc
-        from renderer import rendering
-        from losses import total_variation_loss, get_disparity_smoothness, distortion_loss, \\
-            mse_masked, mae_masked, compute_depth_loss, compute_sf_smooth_loss, compute_sf_lke_loss
-        import json, sys
-        names = dict(Embedding=Embedding, MVSNeRF=MVSNeRF, MVSNet=MVSNet, MVSNeRF_G=MVSNeRF_G, DyMVSNeRF_G=DyMVSNeRF_G,
-                     BasicDiscriminator=BasicDiscriminator, GRAFDiscriminator=GRAFDiscriminator,
-                     build_rays=build_rays, visualize_depth=visualize_depth, projection_from_ndc=projection_from_ndc,
-                     rendering=rendering, distortion_loss=distortion_loss, mse_masked=mse_masked)
-        if __name__ == "__main__":
-            print("ARGV " + json.dumps(sys.argv[1:]))
-            print("BOUND " + json.dumps({k: v.__module__ for k, v in names.items()}))
-    """,
-}
-
-
-@pytest.fixture
-def caller_dir(tmp_path):
-    for name, src in STANDINS.items():
-        (tmp_path / name).write_text(textwrap.dedent(src))
-    return str(tmp_path)
-
-
-@pytest.fixture
-def clean_modules():
-    names = ("utils", "renderer", "networks", "losses", "train_imports", "inplace_abn")
-    saved = {n: sys.modules.pop(n, None) for n in names}
-    path = list(sys.path)
-    yield
-    import zest_dropin
-    zest_dropin.uninstall()
-    for n in names:
-        sys.modules.pop(n, None)
-        if saved[n] is not None:
-            sys.modules[n] = saved[n]
-    sys.path[:] = path
+from golden_cases import PKG, ROOT
+from package_cases import caller_dir, clean_modules  # noqa: F401  (the stand-in caller modules)
 
 
 def test_package_shadows_nothing():

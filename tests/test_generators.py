@@ -8,7 +8,6 @@ builders - chunk-size invariance, result structure, fp32 and fused bf16 plans.""
 import os
 import socket
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -16,17 +15,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from package_cases import _args, _batch, _generator
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _args(**kw):
-    a = SimpleNamespace(batch_size=64, N_samples=24, pad=4, vis_cnn=False, save_test=".", patch_size=-1,
-                        scale_anneal=-1, gan_type=None, white_bkgd=False, with_chain_loss=True,
-                        use_motion_mask=True, num_extra_samples=16, raw_noise_std=0.0, chunk=256,
-                        img_downscale=1.0, netchunk=4096, feat_dim=20, feat_dim_dy=20,
-                        use_color_volume=False, net_type="v0", precision=32)
-    a.__dict__.update(kw)
-    return a
 
 
 def _shard_worker(rank, world, port, q):
@@ -95,37 +86,6 @@ def test_forward_val_shards_chunks_and_gathers_once():
 
 
 # ------------------------------------------------------------------------------------- GPU
-def _batch(seed, H=32, W=32, V=3, V_dy=3):     # MVSNet's regulariser takes 3 views (32 + 9 channels)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import golden_cases as gc
-    import zest_synth as zs
-    g = zs.rng(seed)
-    inp = gc.rays_inputs(seed, V=V, H=H, W=W)
-    G = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    cost = gc.cost_inputs(seed + 1, V=V + 1, H=H // 4, W=W // 4)
-    cost_dy = gc.cost_inputs(seed + 2, V=V_dy, H=H // 4, W=W // 4)
-    nb_w2cs, nb_intr = zs.make_cameras(V_dy, H, W, focal=30.0)
-    return dict(images=G(inp["imgs"]), proj_mats=G(cost["proj_mats"]), near_fars=G(inp["near_fars"]),
-                w2cs=G(inp["w2cs"]), c2ws=G(inp["c2ws"]), intrinsics=G(inp["intrinsics"]), depths=G(inp["depths"]),
-                time=torch.tensor(3), total_frames=torch.tensor(12), flow_fwds=G(inp["flow_fwd"]),
-                flow_bwds=G(inp["flow_bwd"]), mask_fwds=G(inp["mask_fwd"]), mask_bwds=G(inp["mask_bwd"]),
-                motion_coords=[G(inp["motion_coords"])], nb_imgs=G(g.uniform(0, 1, size=(1, V_dy, 3, H, W)).astype(np.float32)),
-                nb_proj_mats=G(cost_dy["proj_mats"]), nb_w2cs=G(nb_w2cs), nb_intr=G(nb_intr))
-
-
-def _generator(args, train_builders=False):
-    import zest_networks as networks
-    import golden_cases as gc
-    torch.manual_seed(1)
-    mk = lambda P, F, static: networks.MVSNeRF(D=8, W=256, input_ch_pts=P, output_ch=4, input_ch_views=gc.PE_DIR,
-                                               input_ch_feat=F, skips=[4], net_type="v0", sceneflow=True,
-                                               static=static, use_mvs=True).cuda()
-    enc, enc_dy = (networks.MVSNet().cuda().requires_grad_(train_builders),
-                   networks.MVSNet().cuda().requires_grad_(train_builders))
-    return networks.DyMVSNeRF_G(args, 1, mk(gc.PE_XYZT, 20, False), mk(gc.PE_PTS, 20, True), enc, enc_dy,
-                                networks.Embedding(3, 10), networks.Embedding(4, 10), networks.Embedding(3, 4))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("precision", [32, 16])
 def test_forward_val_is_chunk_invariant(hip, precision):

@@ -8,14 +8,13 @@ of builder_grad_cases.py.
 """
 import functools
 
-import numpy as np
 import pytest
 import torch
 
 import builder_grad_cases as bc
+from gpu_cases import DEV, G
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SWITCHES = ((False, False), (True, False), (False, True), (True, True))
 COSTREG_CASES = [(3, (False, False))] + [(1, s) for s in SWITCHES]
 
@@ -283,7 +282,6 @@ def test_builder_chain_backward_at_the_forwards_own_values(hip, monkeypatch):
     net = networks.MVSNet().to(DEV).train()
     _randomise_norms(net, networks)
     inp = gc.cost_inputs(67, V=3, H=8, W=16, pad=4)          # padded volume 128 x 16 x 24, as test_volume_builder_trains_end_to_end
-    G = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     imgs, proj = G(inp["imgs"]), G(inp["proj_mats"])
     kept_f, kept_r = _keeping(net.feature, batched=True), _keeping(net.cost_reg_2, batched=False)
     taken, seen = [], {}

@@ -19,18 +19,14 @@ import cache_cases as cc
 import golden_cases as gc
 import optim_cases as oc
 import zest_synth as zs
-from test_generators import _args, _batch, _generator
+from gpu_cases import DEV, G
+from package_cases import _args, _batch, _generator
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 FEAT, T, M = 20, 6, 45                  # 45 samples: one full 32-sample tile and a ragged one
 DEVICE_CHANGES = cc.WEIGHT_CHANGES + (cc.BY_NAME["adam_step"],)                  # 1 .. 6 and 8
 BUILDER_CHANGES = cc.WEIGHT_CHANGES + cc.NORM_CHANGES + (cc.BY_NAME["adam_step"],)  # 1 .. 8
 ids = lambda cases: [c.name for c in cases]              # noqa: E731
-
-
-def G(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _uniform(seed, *shape):

@@ -7,12 +7,13 @@ Tolerances: split-bf16 operands (passes = 3) carry 16 significant bits per produ
 layer; bf16 operands (passes = 1, the --precision 16 path) 8 bits - 2e-2 of the output scale.  The norm constants
 and the final addition are fp32.
 """
-import numpy as np
 import pytest
 import torch
 
+from gpu_cases import DEV, G
+from judges import max_ratio
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 LAYERS = [(41, 8, 1), (8, 16, 2), (16, 16, 1), (16, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1)]
 
 
@@ -22,11 +23,6 @@ def _cl(x):            # [1,C,D,H,W] -> [D,H,W,C]
 
 def _cf(x):            # [D,H,W,C] -> [1,C,D,H,W]
     return x.permute(3, 0, 1, 2)[None]
-
-
-def _rel(got, want):
-    got, want = got.detach(), want.detach()
-    return float((got - want).abs().max() / want.abs().max().clamp_min(1e-30))
 
 
 @pytest.mark.parametrize("passes,tol", [(3, 2e-4), (1, 2e-2)])
@@ -49,7 +45,7 @@ def test_conv_layer_against_library(hip, cin, cout, stride, passes, tol):
     stats = zest_hip.costreg_stats(cout, DEV)
     got = zest_hip.costreg_conv(_cl(x), pre, networks.CostRegNet._pack_conv(w, passes), cout, stride, passes, stats)
     assert tuple(got.shape) == tuple(want.shape[2:]) + (cout,)
-    assert _rel(_cf(got), want) < tol
+    assert max_ratio(_cf(got), want) < tol
     # the batch statistics are those of the kernel's own output
     flat = got.double().reshape(-1, cout)
     used = int(stats[-1, 0, 0])
@@ -76,7 +72,7 @@ def test_deconv_layer_against_library(hip, cin, cout, two, passes, tol):
     got = zest_hip.costreg_deconv(_cl(x0), p0, _cl(x1) if two else None, p1 if two else None,
                                   networks.CostRegNet._pack_deconv(w, passes), cout, passes, stats)
     assert tuple(got.shape) == (2 * D, 2 * H, 2 * W, cout)
-    assert _rel(_cf(got), want) < tol
+    assert max_ratio(_cf(got), want) < tol
     flat = got.double().reshape(-1, cout)
     used = int(stats[-1, 0, 0])
     assert 1 <= used <= stats.shape[0] - 1
@@ -105,7 +101,7 @@ def test_conv2d_layer_against_library(hip, cin, cout, k, stride, passes, tol):
     got = zest_hip.conv2d_cl(x.permute(0, 2, 3, 1).contiguous(), pre, networks.pack_conv_weights(w, passes), cout, k, stride,
                              passes, stats)
     assert tuple(got.shape) == (N,) + tuple(want.shape[2:]) + (cout,)
-    assert _rel(got.permute(0, 3, 1, 2), want) < tol
+    assert max_ratio(got.permute(0, 3, 1, 2), want) < tol
     used = int(stats[-1, 0, 0])
     assert torch.allclose(stats[:used].sum(0)[0], got.double().reshape(-1, cout).sum(0), rtol=1e-5, atol=1e-4)
 
@@ -127,7 +123,7 @@ def test_feature_pyramid_against_library(hip, training, passes, tol):
         want = ref(imgs)[0]
         got = net.forward_hip(imgs, passes=passes)
     assert tuple(got.shape) == (3, 10, 18, 32) and tuple(want.shape) == (3, 32, 10, 18)
-    assert _rel(got.permute(0, 3, 1, 2), want) < tol
+    assert max_ratio(got.permute(0, 3, 1, 2), want) < tol
     for a, b in zip(net.modules(), ref.modules()):
         if isinstance(a, networks.ActivatedBatchNorm):
             assert int(a.num_batches_tracked) == int(b.num_batches_tracked) == (1 if training else 0)
@@ -167,7 +163,6 @@ def test_cost_volume_channels_last_equals_planes(hip):
     import golden_cases as gc
     import zest_hip
     c = gc.cost_inputs(5, V=3, H=12, W=20)
-    G = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     feats, proj, depth = G(c["feats"])[0], G(c["proj_mats"])[0, 1:], G(c["depth_values"])[0]
     imgs = torch.nn.functional.interpolate(G(c["imgs"])[0], (12, 20), mode="bilinear", align_corners=False)
     planes, _ = zest_hip.volume_cost(feats, imgs, proj, depth, pad=2)
@@ -195,7 +190,7 @@ def test_regularisation_net_against_library(hip, training, passes, tol):
         want, _ = ref(cost[:, :41])
         got = net.forward_hip(_cl(cost), passes=passes)
     assert tuple(got.shape) == tuple(want.shape) == (1, 8, D, H, W)
-    assert _rel(got, want) < tol
+    assert max_ratio(got, want) < tol
     for a, b in zip(net.modules(), ref.modules()):
         if isinstance(a, networks.ActivatedBatchNorm):
             assert int(a.num_batches_tracked) == int(b.num_batches_tracked) == (1 if training else 0)
@@ -207,18 +202,18 @@ def test_regularisation_net_against_library(hip, training, passes, tol):
     with torch.no_grad():
         net.conv2.conv.weight.mul_(1.5), ref.conv2.conv.weight.mul_(1.5)
         net.conv9[0].weight.mul_(0.5), ref.conv9[0].weight.mul_(0.5)
-        assert _rel(net.forward_hip(_cl(cost), passes=passes), ref(cost[:, :41])[0]) < tol
+        assert max_ratio(net.forward_hip(_cl(cost), passes=passes), ref(cost[:, :41])[0]) < tol
         # ... and when a parameter OBJECT is replaced (a fresh tensor at version 0)
         for m in (net, ref):
             m.conv4.conv.weight = torch.nn.Parameter(m.conv4.conv.weight.detach() * 0.5)
-        assert _rel(net.forward_hip(_cl(cost), passes=passes), ref(cost[:, :41])[0]) < tol
+        assert max_ratio(net.forward_hip(_cl(cost), passes=passes), ref(cost[:, :41])[0]) < tol
 
 
 @pytest.mark.parametrize("precision", [32, 16])
 def test_builder_takes_the_hip_net_without_a_graph(hip, precision, monkeypatch):
     """MVSNet.forward under no_grad: plane sweep + HIP nets == plane sweep + library nets; what it takes with autograd
     recording."""
-    import test_generators as tg
+    import package_cases as tg
     import zest_networks as networks
     x = tg._batch(17)
     net = networks.MVSNet().to(DEV)
@@ -233,7 +228,7 @@ def test_builder_takes_the_hip_net_without_a_graph(hip, precision, monkeypatch):
         want = net(imgs, proj, nf, pad=4)[0].float()
     assert len(calls) == 1 and calls[0]["passes"] == (1 if precision == 16 else 3)
     assert tuple(got.shape) == tuple(want.shape) == (1, 8, 128, 16, 16)
-    assert _rel(got, want) < (1e-3 if precision == 32 else 0.1)
+    assert max_ratio(got, want) < (1e-3 if precision == 32 else 0.1)
     net.zest_hip_costreg = True
     net.requires_grad_(True)
     with amp:
@@ -279,7 +274,7 @@ def test_regularisation_net_trains_through_the_hip_forward(hip, passes, tol):
     want.backward(g_out)
     got = zest_autograd.costreg_apply(net, ca, passes)
     got.backward(g_out)
-    assert _rel(got, want) < (1e-3 if passes == 3 else 6e-2)
+    assert max_ratio(got, want) < (1e-3 if passes == 3 else 6e-2)
     l2 = lambda a, b: float((a - b).norm() / b.norm().clamp_min(1e-30))
     assert l2(ca.grad, cb.grad) < tol
     for (name, p), (_, q) in zip(net.named_parameters(), ref.named_parameters()):
@@ -310,7 +305,7 @@ def test_feature_pyramid_trains_through_the_hip_forward(hip, passes, tol):
     want.backward(g_out)
     got = zest_autograd.feature_apply(net, imgs, passes)
     got.backward(g_out)
-    assert tuple(got.shape) == tuple(want.shape) and _rel(got, want) < (1e-3 if passes == 3 else 6e-2)
+    assert tuple(got.shape) == tuple(want.shape) and max_ratio(got, want) < (1e-3 if passes == 3 else 6e-2)
     l2 = lambda a, b: float((a - b).norm() / b.norm().clamp_min(1e-30))
     for (name, p), (_, q) in zip(net.named_parameters(), ref.named_parameters()):
         assert p.grad is not None and l2(p.grad, q.grad) < tol, name

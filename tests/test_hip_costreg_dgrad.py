@@ -6,9 +6,9 @@ import pytest
 import torch
 
 import dgrad_cases as dc
+from gpu_cases import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 # extents: one voxel; one short row; ragged in every axis; a row longer than one tile in x with a ragged tail
 # (50 = 32 + 16 + 2); whole tiles; several tiles; more tiles than a workgroup's four waves take at once; exactly the
@@ -152,7 +152,7 @@ def test_both_switches_reach_costreg_apply_as_arguments(hip, monkeypatch):
     the builder fixes) with zest_autograd.costreg_apply replaced by a recorder: for all four settings of
     MVSNet.zest_hip_costreg_wgrad / zest_hip_costreg_dgrad both keyword values equal the attributes, and the forward
     pass assigns no attribute of cost_reg_2."""
-    import test_generators as tg
+    import package_cases as tg
     import zest_autograd
     import zest_networks as networks
     x = tg._batch(17, H=64, W=96)

@@ -73,8 +73,10 @@ Largest observed |err| / (eps A) per layer, MI355X (information, not the limit; 
 import pytest
 import torch
 
+from gpu_cases import DEV
+from judges import check_elements, check_stats, max_ratio
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 U = 2.0 ** -9
 F = torch.nn.functional
 
@@ -122,45 +124,7 @@ def deconv_ref(xin, w):
     return buf[1:, 1:, 1:]
 
 
-# ------------------------------------------------------------------------------------------------ checks
-def check_elements(name, got, want, A, eps, rows_per_tile=None):
-    """Every element within eps A + 2^-23 |want|; on failure: how many, and where the worst one sits (slice, row, x
-    block and lane, channel; for a convolution also the row within its group; the parity class of a transposed one)."""
-    err = (got.double() - want).abs()
-    bound = eps * A + 2.0 ** -23 * want.abs()
-    assert bool(torch.isfinite(want).all()) and bool(torch.isfinite(A).all()), "%s: the reference or its magnitude is not finite" % name
-    ratio = float((err / (eps * A).clamp_min(1e-300))[A > 0].max())
-    print("RATIO %-58s max |err| / (eps A) = %.4f   (eps %.3e)" % (name, ratio, eps))
-    bad = ~(err <= bound)                                    # not `err > bound`: a NaN error is bad
-    if bool(bad.any()):
-        n_bad = int(bad.sum())
-        over = torch.where(bad, (err / bound.clamp_min(1e-300)).nan_to_num(nan=float("inf"), posinf=float("inf")), torch.zeros_like(err))
-        z, y, x, c = (int(v) for v in torch.unravel_index(over.argmax(), over.shape))
-        idx = bad.nonzero()
-        rows, slices = torch.unique(idx[:, 1])[:24].tolist(), torch.unique(idx[:, 0])[:24].tolist()
-        where = "z %d y %d x %d (x block %d, lane %d) channel %d" % (z, y, x, x // 16, x % 16, c)
-        if rows_per_tile:
-            where += "; row %d of its group of %d" % (y % rows_per_tile, rows_per_tile)
-        else:
-            where += "; parity class (%d, %d, %d)" % (z & 1, y & 1, x & 1)
-        raise AssertionError("%s: %d of %d elements past the bound; worst at %s: got %.9g want %.9g err %.3g bound %.3g; "
-                             "failing rows y (first 24): %s; failing slices z (first 24): %s"
-                             % (name, n_bad, bad.numel(), where, float(got[z, y, x, c]), float(want[z, y, x, c]),
-                                float(err[z, y, x, c]), float(bound[z, y, x, c]), rows, slices))
-    return ratio
-
-
-def check_stats(name, stats, got, n_wg):
-    rows = stats.shape[0] - 1
-    used = int(stats[-1, 0, 0])
-    assert used == n_wg and 1 <= used <= rows, (name, used, n_wg)
-    assert bool(torch.isfinite(stats[:used]).all()), name
-    assert bool(torch.isnan(stats[used:rows]).all()), "%s: a statistics row past the %d in use was written" % (name, used)
-    flat = got.double().reshape(-1, got.shape[-1])
-    assert torch.allclose(stats[:used].sum(0)[0], flat.sum(0), rtol=1e-5, atol=1e-4), name
-    assert torch.allclose(stats[:used].sum(0)[1], flat.square().sum(0), rtol=1e-5, atol=1e-4), name
-
-
+# ------------------------------------------------------------------------------------------------ inputs
 def new_stats(cout):
     import zest_hip
     stats = zest_hip.costreg_stats(cout, DEV)
@@ -449,11 +413,6 @@ def test_bn_bwd_against_float64_autograd(hip, C, big):
 
 
 # ------------------------------------------------------------------------------------------------ g: the nets at full size
-def _rel(got, want):
-    got, want = got.detach(), want.detach()
-    return float((got - want).abs().max() / want.abs().max().clamp_min(1e-30))
-
-
 def _randomise_norms(net):
     import zest_networks as networks
     with torch.no_grad():
@@ -483,7 +442,7 @@ def test_regularisation_net_at_the_nsff_volume(hip, training, passes, tol):
         got = net.forward_hip(cost, passes=passes)
         want, _ = ref(cost[..., :41].permute(3, 0, 1, 2)[None])
     assert tuple(got.shape) == tuple(want.shape) == (1, 8, D, H, W)
-    assert _rel(got, want) < tol
+    assert max_ratio(got, want) < tol
     for a, b in zip(net.modules(), ref.modules()):
         if isinstance(a, networks.ActivatedBatchNorm):
             assert int(a.num_batches_tracked) == int(b.num_batches_tracked) == (1 if training else 0)
@@ -508,7 +467,7 @@ def test_feature_pyramid_at_the_nsff_image_size(hip, training, passes, tol):
         want = ref(imgs)[0]
         got = net.forward_hip(imgs, passes=passes)
     assert tuple(got.shape) == (3, 120, 176, 32) and tuple(want.shape) == (3, 32, 120, 176)
-    assert _rel(got.permute(0, 3, 1, 2), want) < tol
+    assert max_ratio(got.permute(0, 3, 1, 2), want) < tol
     for a, b in zip(net.modules(), ref.modules()):
         if isinstance(a, networks.ActivatedBatchNorm):
             assert int(a.num_batches_tracked) == int(b.num_batches_tracked) == (1 if training else 0)

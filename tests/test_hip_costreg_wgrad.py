@@ -6,9 +6,9 @@ import pytest
 import torch
 
 import wgrad_cases as wc
+from gpu_cases import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 
 # extents: one voxel; one short row; ragged in every axis; a row of two chunks (50 = 32 + 18); whole units; several
 # chunks and units; more units than one per workgroup needs; exactly the workgroup cap (768 units: the smallest such

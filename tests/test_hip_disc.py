@@ -3,7 +3,7 @@ zest_autograd.GrafDiscFn, zest_losses.train_step_loss / discriminator_step_loss)
 (tests/golden/disc_*.npz) and, at the smallest shapes where the kernels can go wrong, against the float64 restatement in
 disc_cases.py.
 
-Bounds: logits, losses, u and v within test_hip_ops' ATOL + RTOL |want|; gradients within ATOL max|want| + RTOL |want| per
+Bounds: logits, losses, u and v within judges' ATOL + RTOL |want|; gradients within ATOL max|want| + RTOL |want| per
 element, every element counted (the bound of test_hip_patch_terms.py).  disc_cases.inputs asserts on the host, before a
 comparison, that no leaky-ReLU input sits closer to 0 than 10 times the fp32 deviation, so no element is excused.  At the
 production shape (ndf 64, imsize 64), where no seed keeps clear of the kink, gradients are compared by relative L2 norm
@@ -17,7 +17,8 @@ import torch
 
 import disc_cases as dc
 import patch_cases as pc
-from test_hip_ops import G, close, ATOL, RTOL, DEV
+from gpu_cases import G, DEV
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -30,44 +31,6 @@ def _disc(imsize, ndf, seed, train=True):
 
 def _steps(B, imsize, ndf, seed, digests=False):
     return dc.run_steps(lambda: _disc(imsize, ndf, seed), B, imsize, ndf, seed, digests=digests, as_tensor=G)
-
-
-def _close_grad(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), name
-    assert np.abs(want).max() > 0, name
-    close(got, want, atol=ATOL * np.abs(want).max(), name=name)
-
-
-def _close_l2(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), name
-    assert np.isfinite(want).all() and np.linalg.norm(want) > 0, name
-    rel = np.linalg.norm(got - want) / np.linalg.norm(want)
-    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)               # false for a NaN
-
-
-def _compare(got, want, imsize, ndf, name, digests=False):
-    """A dict of disc_cases.run_steps against the fixture's or the restatement's."""
-    assert sorted(got) == sorted(k for k in want if k != "seed")
-    for k, v in got.items():
-        w, tag = np.asarray(want[k], np.float64), "%s: %s" % (name, k)
-        if k == "gen__grad__rgb":
-            (_close_l2 if digests else _close_grad)(v, w, tag)
-        elif k.startswith("disc__grad__"):
-            _close_grad(v, w, tag)
-        elif k.startswith("disc__grad_norm__"):
-            assert np.isfinite(v) and np.isfinite(w), (tag, v, w)
-            assert abs(v - w) <= RTOL * w, (tag, v, w)
-        elif k.startswith("disc__grad_dots__"):
-            i = int(k.rsplit("__", 1)[1])
-            shape = dc.state(imsize, ndf, 0)["main.%d.weight_orig" % i].shape
-            d_norm = np.linalg.norm(dc.directions(imsize, ndf, i, shape).reshape(dc.N_DIRS, -1), axis=1)
-            bound = RTOL * np.asarray(want["disc__grad_norm__%d" % i], np.float64) * d_norm
-            assert np.isfinite(v).all() and np.isfinite(w).all() and np.isfinite(bound).all(), (tag, v, w, bound)
-            assert not (~(np.abs(v - w) <= bound)).any(), (tag, v, w, bound)
-        else:
-            close(np.atleast_1d(v), np.atleast_1d(w), name=tag)
 
 
 @pytest.mark.parametrize("case", dc.CASES, ids=lambda c: "%dx%d_ndf%d" % c)
@@ -83,7 +46,7 @@ def test_fixture(hip, case):
     if not digests:
         dc.inputs(B, imsize, ndf, seed)
     got = _steps(B, imsize, ndf, seed, digests)
-    _compare(got, fx, imsize, ndf, str(case), digests)
+    dc.compare(got, fx, imsize, ndf, str(case), digests)
 
     inp = dc.patches(B, imsize, seed)
     D = _disc(imsize, ndf, seed)
@@ -108,7 +71,7 @@ def test_fixture(hip, case):
 def test_restatement(hip, size):
     B, imsize, ndf = size
     seed, _, _ = dc.inputs(B, imsize, ndf)
-    _compare(_steps(B, imsize, ndf, seed), dc.restated(B, imsize, ndf), imsize, ndf, str(size))
+    dc.compare(_steps(B, imsize, ndf, seed), dc.restated(B, imsize, ndf), imsize, ndf, str(size))
 
 
 def test_constant_patch_pins_the_padding(hip):
@@ -182,7 +145,7 @@ def test_two_forwards_one_backward(hip):
     pa, pb = dict(first.named_parameters()), dict(second.named_parameters())
     for i, m in zip(dc.INDICES[imsize], D.layers()):
         k = "main.%d.weight_orig" % i
-        _close_grad(m.weight_orig.grad.cpu().numpy(), (pa[k].grad + pb[k].grad).numpy(), k)
+        scaled_close(m.weight_orig.grad.cpu().numpy(), (pa[k].grad + pb[k].grad).numpy(), k, ATOL, RTOL, nonzero=True)
     # accumulation: a second backward into the existing .grad adds
     once = [m.weight_orig.grad.clone() for m in D.layers()]
     D2 = _disc(imsize, ndf, seed)
@@ -237,7 +200,7 @@ def test_train_step_loss_adds_the_adversarial_term(hip):
     assert torch.equal(logs["G_fake_loss"], g_fake.detach()) and not logs["G_fake_loss"].requires_grad
     assert sorted(set(logs) - set(logs0)) == ["G_fake_loss"]
     close(total.detach().reshape(1), (base.detach() + g_fake.detach()).double().cpu().numpy().reshape(1), name="total")
-    _close_grad(r1["rgb_map"].grad.cpu().numpy(), (r0["rgb_map"].grad + r2["rgb_map"].grad).double().cpu().numpy(), "rgb_map")
+    scaled_close(r1["rgb_map"].grad.cpu().numpy(), (r0["rgb_map"].grad + r2["rgb_map"].grad).double().cpu().numpy(), "rgb_map", ATOL, RTOL, nonzero=True)
     for k in ("depth_map", "weights"):
         assert torch.equal(r1[k].grad, r0[k].grad), k
     assert all(m.weight_orig.grad is None for m in D.layers())

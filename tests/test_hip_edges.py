@@ -6,7 +6,8 @@ import pytest
 import torch
 
 import golden_cases as gc
-from test_hip_ops import G, close, _mlp_setup
+from gpu_cases import _mlp_setup, render_scene
+from judges import close
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +45,6 @@ def test_empty_batches_return_empty_results(hip):
 
 def test_empty_batch_through_rendering(hip):
     """rendering() on zero rays, fused and per-operator plans: every key of the result dict, empty."""
-    from test_hip_render import render_scene
     sc = gc.render_inputs(77, R=4, S=16, V=3, use_mvs=True, scene_flow=True, use_mvs_dy=True)
     for k in ("rays_pts", "rays_ndc", "depth_candidates", "rays_dir"):
         sc[k] = sc[k][:, :0]

@@ -26,8 +26,7 @@ import torch
 
 import engine_format_cases as ef
 import golden_cases as gc
-from test_hip_ops import G
-from test_hip_render import build_nets, render_scene
+from gpu_cases import G, _mlp_table, build_nets, render_scene
 
 pytestmark = pytest.mark.gpu
 CASE = dict(val=True)
@@ -36,16 +35,6 @@ KW = {"bf16": dict(precision=16, dtype16="bf16"), "f16": dict(precision=16, dtyp
 
 def _prec(zh, fmt):
     return {"bf16": zh.PREC_BF16, "f16": zh.PREC_F16, "f16x3": zh.PREC_F16X3}[fmt]
-
-
-def _desc_and_table(zh, inp):
-    """MlpDesc and parameter table of an engine_format_cases.mlp_case (the recipe of test_hip_ops._mlp_setup)."""
-    head = zh.HEAD_NONE
-    if inp["sceneflow"] and inp["net_type"] == "v0":
-        head = zh.HEAD_BLEND if inp["static"] else zh.HEAD_DYNAMIC
-    use_feat = inp["use_mvs"] or inp["net_type"] == "v2"
-    desc = zh.MlpDesc(inp["P"], inp["Fd"], gc.PE_DIR, int(use_feat), 2 if inp["net_type"] == "v2" else 0, head)
-    return desc, zh.param_table({k: G(v) for k, v in inp["state"].items()}, desc)
 
 
 def _fold_terms(zh, desc, packed, prec):
@@ -60,7 +49,7 @@ def _packed(case, fmt):
     """(desc, packed buffer, (Wc, bc) of its fold scratch) of a standalone case.  Cached: callers must not mutate the result."""
     import zest_hip as zh
     inp, _ = ef.mlp_case(case, fmt if fmt != "f16x3" else "bf16")
-    desc, tab = _desc_and_table(zh, inp)
+    desc, tab = _mlp_table(zh, inp)
     packed = zh.mlp_pack(desc, _prec(zh, fmt), tab)
     terms = _fold_terms(zh, desc, packed, _prec(zh, fmt)) if fmt != "f16x3" else None
     return desc, packed, terms

@@ -18,26 +18,13 @@ import torch
 import golden_cases as gc
 import oracle_run as orun
 import zest_synth as zs
+from gpu_cases import DEV, G
+from judges import finite_close, ATOL, RTOL
 from oracle import zest_oracle as zo
 
 pytestmark = pytest.mark.gpu
-ATOL, RTOL = 1e-4, 1e-3          # the project's fp32-class tolerance (BASELINE.json)
-DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plain_stream_sha256.json")
 FOLD_SCRATCH_BYTES = 129 * 1024   # Wc [128][256] + bc [128] in fp32, padded to KiB (include/zest_render.h)
-
-
-def G(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def elements_close(got, want):
-    """1e-4 abs + 1e-3 rel on every element against a finite float64 reference; a non-finite error is outside it."""
-    assert np.isfinite(want).all()
-    err = np.abs(got - want)
-    bad = ~(err <= ATOL + RTOL * np.abs(want))
-    assert not bad.any(), "%d/%d outside 1e-4 + 1e-3 rel (%d not finite), max err %.3g" % (
-        bad.sum(), bad.size, (~np.isfinite(got)).sum(), np.nanmax(err))
 
 
 def _state(Fd, use_mvs, seed, lively):
@@ -66,7 +53,7 @@ def test_fold_arithmetic_with_bias_meets_fp32_tolerance_against_float64(hip, use
     print("fold arithmetic (%s): max err %.3g, rms err %.3g, max |ref| %.3g, rgb spread %.3g"
           % ("features" if use_mvs else "no features", err.max(), np.sqrt((err ** 2).mean()), np.abs(want).max(),
              want[:, :3].std()))
-    elements_close(got, want)
+    finite_close(got, want, "fold", ATOL, RTOL)
     # the check has teeth: without the Wvh bf term the rgb outputs would sit far outside the tolerance
     sd = orun.state_t(state, torch.float64)
     sd["nerf.feature_linear.bias"] = torch.zeros(256, dtype=torch.float64)

@@ -11,7 +11,7 @@ test_fwd_edges_cpu.py guards the inputs and shows that each judge rejects a wron
   build_rays                      S = 1, 2, 65; R S = 1, 255, 257; jitter absent, all 0, all 1 - 2^-24
   sample_pdf                      1 ... 512 bins in probability space; zero / spike / half-dead weights; u = 0, 1 - 2^-24, 1
 
-Rule (fwd_edge_cases.tight): every element within 1e-4 + 1e-3 |want| (test_hip_ops.close: a one-sided NaN fails), and per
+Rule (fwd_edge_cases.tight): every element within 1e-4 + 1e-3 |want| (judges.close: a one-sided NaN fails), and per
 output tensor max|got - want64| <= F spread + 4 2^-24 max|want|, spread = max|oracle_fp32 - oracle_fp64|, F = 8.  PE columns
 of encode: 2e-6 absolute.  sample_pdf: |F(got) - u| <= 4 c + 2^-22.  Every test prints the worst error / spread it saw
 (spread floored at 2^-24 max|want|).  Measured on an MI355X:
@@ -39,7 +39,7 @@ import torch
 
 import fwd_edge_cases as fe
 import grad_edge_cases as ge
-from test_hip_ops import G
+from gpu_cases import G
 
 pytestmark = pytest.mark.gpu
 

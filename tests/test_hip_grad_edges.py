@@ -9,7 +9,7 @@
   fp32 MLP backward                     ragged row blocks and the split weight-gradient products with and without remainder
 
 Rule: |got - want| <= 1e-3 max_row|want| + 1e-3 |want| (grad_edge_cases.rows_close); the scattered volume gradient and the
-MLP parameter gradients per tensor (tensor_close, test_hip_backward.gclose).  Rows and voxels whose reference is zero
+MLP parameter gradients per tensor (tensor_close, backward_cases.gclose).  Rows and voxels whose reference is zero
 are exactly zero.  Every test prints the worst |got - want| / max|want| it saw.  Measured on an MI355X:
 
   family                                         worst err / row (tensor) max
@@ -31,7 +31,8 @@ import torch
 
 import golden_cases as gc
 import grad_edge_cases as ge
-from test_hip_ops import G, close, _mlp_module
+from gpu_cases import G, _mlp_module
+from judges import close
 
 pytestmark = pytest.mark.gpu
 

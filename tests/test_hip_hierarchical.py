@@ -10,8 +10,8 @@ import torch
 
 import golden_cases as gc
 import oracle_run
-from test_hip_ops import G, close, ATOL, RTOL
-from test_hip_render import build_nets
+from gpu_cases import G, build_nets
+from judges import close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,7 @@
 """GPU: csrc/image_metrics.hip (mse, psnr, ssim of a frame in two launches) against the float64 restatement of
 tests/metrics_cases.py.
 
-Bounds: the project's own (test_hip_ops.ATOL, RTOL = 1e-4 + 1e-3 |want|) on mse and ssim, on psnr relative to its value,
+Bounds: the project's own (judges.ATOL, RTOL = 1e-4 + 1e-3 |want|) on mse and ssim, on psnr relative to its value,
 and PER PIXEL on the SSIM map and the error map; no element is excused (the function has no kinks).  The fp32 torch
 composition on a CPU, which takes E[x^2] - mu^2 as it stands, comes within 0.57 of the per-pixel bound on the near-flat
 case, within 0.33 on the other smooth ones and within 0.01 on the noisy one, and its means within 1e-6: the bound is
@@ -9,30 +9,25 @@ reachable.  The kernel takes the moments about a pivot and came within 0.14 of i
 figures).  Layouts, repeated calls and the optional outputs are compared bit for bit: the kernel orders every sum
 itself, and a layout changes addresses only.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import lpips_cases as lc
 import metrics_cases as mc
-from test_hip_ops import ATOL, RTOL
+from gpu_cases import DEV
+from judges import finite_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 def _dev(a):
     return torch.from_numpy(np.array(a)).to(DEV)
 
 
-def _close(got, want, what):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.isfinite(want).all() and np.isfinite(got).all(), "%s: non-finite entries" % what
-    err = np.abs(got - want)
-    bound = ATOL + RTOL * np.abs(want)
-    print("%s: worst error / bound = %.4f" % (what, float((err / bound).max())))
-    assert not (~(err <= bound)).any(), (what, float((err / bound).max()))
+_close = functools.partial(finite_close, atol=ATOL, rtol=RTOL, show=True)      # prints each worst error / bound
 
 
 def _check_case(case, ws=5):

@@ -5,7 +5,8 @@ import pytest
 import torch
 
 import golden_cases as gc
-from test_hip_ops import G, close, ATOL, RTOL
+from gpu_cases import G
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -46,5 +47,5 @@ def test_projection_from_ndc_matches_reference(hip):
     (uv * G(inp["gw"])).sum().backward()
     scale = np.abs(gold["uv"]).max()
     close(uv[0], gold["uv"], atol=ATOL * scale, name="uv")
-    close(w.grad[0], gold["uv_dw"], atol=ATOL * np.abs(gold["uv_dw"]).max(), name="d uv / d weights")
-    close(pts.grad[0], gold["uv_dpts"], atol=ATOL * np.abs(gold["uv_dpts"]).max(), name="d uv / d pts")
+    scaled_close(w.grad[0], gold["uv_dw"], "d uv / d weights", ATOL, RTOL)
+    scaled_close(pts.grad[0], gold["uv_dpts"], "d uv / d pts", ATOL, RTOL)

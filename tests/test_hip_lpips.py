@@ -3,7 +3,7 @@ zest_losses.perceptual_loss / train_step_loss) against the float64 restatement i
 
 Bounds: every layer's term within RTOL |want| of float64, with no absolute term (torch's own fp32 sits below 1e-6
 relative per layer; layers 3-5 are 100 times smaller than layer 1, so the suite's ATOL on the sum would hide a broken
-deep layer); the total with test_hip_ops' close.  Gradients of the small shapes within ATOL max|want| + RTOL |want| per
+deep layer); the total with judges' close.  Gradients of the small shapes within ATOL max|want| + RTOL |want| per
 element, every element counted - lpips_cases.inputs asserts on the host that no ReLU input and no pooling tie sits closer
 than 10 times the fp32 deviation, so no element is excused - and once more with each layer ALONE (the other four lin
 weights zero): layer 1's gradient, 100 times the others', would otherwise hide the deep chains under ATOL max|want|.
@@ -17,7 +17,8 @@ import torch
 import disc_cases as dc
 import lpips_cases as lc
 import patch_cases as pc
-from test_hip_ops import G, close, ATOL, RTOL, DEV
+from gpu_cases import G, DEV
+from judges import close, l2_close, relative_close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -25,29 +26,6 @@ pytestmark = pytest.mark.gpu
 def _net(st):
     import zest_networks
     return lc.load(zest_networks.LPIPS(net='alex'), st, torch.float32, DEV).eval()
-
-
-def _layers_close(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and (want > 0).all() and np.isfinite(want).all(), name
-    assert np.isfinite(got).all(), "%s: non-finite layer terms %s" % (name, got)
-    rel = np.abs(got - want) / want
-    assert not (~(rel <= RTOL)).any(), "%s: per-layer relative error %s" % (name, rel)
-
-
-def _grad_close(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), name
-    assert np.abs(want).max() > 0, name
-    close(got, want, atol=ATOL * np.abs(want).max(), name=name)
-
-
-def _l2_close(got, want, name):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), name
-    assert np.isfinite(want).all() and np.linalg.norm(want) > 0, name
-    rel = np.linalg.norm(got - want) / np.linalg.norm(want)
-    assert rel <= RTOL, "%s: relative L2 error %.3g" % (name, rel)               # false for a NaN
 
 
 def _run(P, in0, in1, backward=True, **kw):
@@ -66,9 +44,9 @@ def test_values_and_gradient_per_element(hip, case):
     seed, st, in0, in1 = lc.inputs(*case)
     want = lc.restated(*case)
     total, layers, grad = _run(_net(st), in0, in1)
-    _layers_close(layers, want["layers"], "%s: layers" % (case,))
+    relative_close(layers, want["layers"], "%s: layers" % (case,), RTOL)
     close(total, want["total"], name="total")
-    _grad_close(grad, want["grad"], "%s: gradient" % (case,))
+    scaled_close(grad, want["grad"], "%s: gradient" % (case,), ATOL, RTOL, nonzero=True)
 
 
 @pytest.mark.parametrize("case", lc.ELEMENT_CASES[:2], ids=lambda c: "%dx%dx%d" % c)
@@ -87,8 +65,8 @@ def test_each_layer_alone(hip, case):
                     w.zero_()
         total, layers, grad = _run(P, in0, in1)
         assert (np.delete(layers, k, 0) == 0).all(), k
-        _layers_close(layers[k], want["layers"][k], "%s: layer %d alone" % (case, k + 1))
-        _grad_close(grad, want["layer_grads"][k], "%s: gradient of layer %d alone" % (case, k + 1))
+        relative_close(layers[k], want["layers"][k], "%s: layer %d alone" % (case, k + 1), RTOL)
+        scaled_close(grad, want["layer_grads"][k], "%s: gradient of layer %d alone" % (case, k + 1), ATOL, RTOL, nonzero=True)
 
 
 def test_production_shape(hip):
@@ -96,16 +74,16 @@ def test_production_shape(hip):
     seed, st, in0, in1 = lc.inputs(*case, check=False)
     want = lc.restated(*case)
     total, layers, grad = _run(_net(st), in0, in1)
-    _layers_close(layers, want["layers"], "layers")
+    relative_close(layers, want["layers"], "layers", RTOL)
     close(total, want["total"], name="total")
-    _l2_close(grad, want["grad"], "gradient")
+    l2_close(grad, want["grad"], "gradient", RTOL)
     for k in range(5):                                     # ... and of each layer alone, by the same norm
         P = _net(st)
         with torch.no_grad():
             for j in range(5):
                 if j != k:
                     getattr(P, "lin%d" % j).model["1"].weight.zero_()
-        _l2_close(_run(P, in0, in1)[2], want["layer_grads"][k], "gradient of layer %d alone" % (k + 1))
+        l2_close(_run(P, in0, in1)[2], want["layer_grads"][k], "gradient of layer %d alone" % (k + 1), RTOL)
 
 
 def test_ragged_frame_forward(hip):
@@ -114,7 +92,7 @@ def test_ragged_frame_forward(hip):
     want = lc.restated(*case, backward=False)
     with torch.no_grad():
         total, layers, _ = _run(_net(st), in0, in1, backward=False)
-    _layers_close(layers, want["layers"], "layers")
+    relative_close(layers, want["layers"], "layers", RTOL)
     close(total, want["total"], name="total")
 
 
@@ -147,8 +125,8 @@ def test_normalize_and_input_forms(hip):
     theirs = _run(P, 2 * unit0 - 1, 2 * unit1 - 1)
     ours = _run(P, unit0, unit1, normalize=True)
     assert np.allclose(ours[0], theirs[0], rtol=1e-5, atol=0) and np.allclose(ours[1], theirs[1], rtol=1e-5, atol=0)
-    _grad_close(ours[2], 2 * theirs[2], "normalize: gradient")       # d / d unit = 2 d / d (2 unit - 1)
-    _layers_close(theirs[1], lc.restated(*case)["layers"], "2 x - 1")
+    scaled_close(ours[2], 2 * theirs[2], "normalize: gradient", ATOL, RTOL, nonzero=True)       # d / d unit = 2 d / d (2 unit - 1)
+    relative_close(theirs[1], lc.restated(*case)["layers"], "2 x - 1", RTOL)
     # channels-last images, read in place: the same numbers bit for bit, the gradient in the input's own layout
     x = G(np.ascontiguousarray(in0.transpose(0, 2, 3, 1))).requires_grad_(True)
     y = G(np.ascontiguousarray(in1.transpose(0, 2, 3, 1)))
@@ -193,7 +171,7 @@ def test_pixel_of_norm_zero(hip):
     ref(x64, torch.from_numpy(in1).double()).sum().backward()
     P = _net(st)
     total, layers, grad = _run(P, in0, in1)
-    _l2_close(grad, x64.grad.numpy(), "gradient")
+    l2_close(grad, x64.grad.numpy(), "gradient", RTOL)
     result, saved = zest_hip.lpips_fwd(G(in0), G(in1), P.packed())
     tap = zest_hip.lpips_saved_views(saved, 1, 31, 31)[0]
     assert tuple(tap.shape) == (2, 7, 7, 64) and float(tap[0, 3, 3].abs().max()) == 0.0 and float(tap[0].max()) > 0
@@ -244,7 +222,7 @@ def test_train_step_loss_adds_the_perceptual_term(hip):
     close(total.detach().reshape(1), (base.detach() + d.detach()).double().cpu().numpy().reshape(1), name="total")
     want = (r0["rgb_map"].grad + r2["rgb_map"].grad).double().cpu().numpy()
     got = r1["rgb_map"].grad.double().cpu().numpy()
-    close(got, want, atol=ATOL * np.abs(want).max(), name="rgb_map")
+    scaled_close(got, want, "rgb_map", ATOL, RTOL)
     assert float(r2["rgb_map"].grad.abs().max()) > 0
     for k in ("depth_map", "weights"):
         assert torch.equal(r1[k].grad, r0[k].grad), k

@@ -9,46 +9,10 @@ import pytest
 import torch
 
 import golden_cases as gc
-import oracle_run
+from gpu_cases import G, ALL_MLP_CASES, MLP_CASES, SHAPE_MLP_CASES, _mlp_module, _mlp_setup
+from judges import close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
-ATOL, RTOL = 1e-4, 1e-3
-DEV = "cuda:0"
-
-
-def G(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def same_nonfinite(got, want):
-    """Where two float64 arrays hold the same non-finite value: NaN in both, or the same infinity."""
-    return (np.isnan(got) & np.isnan(want)) | (np.isinf(want) & (got == want))
-
-
-def wild(got, want):
-    """Where exactly one side is non-finite, or both are and differ: never within any tolerance."""
-    return ~(np.isfinite(got) & np.isfinite(want)) & ~same_nonfinite(got, want)
-
-
-def close(got, want, atol=ATOL, rtol=RTOL, name=""):
-    """Every element within atol + rtol |want|.  A NaN or an infinity passes only against the same value at the same
-    position of `want` (a fixture may pin one); a non-finite error is outside every tolerance."""
-    got = got.detach().double().cpu().numpy() if torch.is_tensor(got) else np.asarray(got, np.float64)
-    want = np.asarray(want, np.float64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    # callers scale atol by max|want|: an infinity in the reference must not become an infinite tolerance
-    assert np.all(np.isfinite(atol)) and np.all(np.isfinite(rtol)), (name, atol, rtol)
-    same = same_nonfinite(got, want)
-    with np.errstate(invalid="ignore"):
-        err = np.where(same, 0.0, np.abs(got - want))
-    tol = atol + rtol * np.where(np.isfinite(want), np.abs(want), 0.0)
-    bad = ~(err <= tol)                                   # not `err > tol`: a NaN error is bad
-    if bad.any():
-        first = np.unravel_index(np.flatnonzero(bad)[0], bad.shape) if bad.ndim else ()
-        finite = np.where(np.isfinite(err), err, -1.0)
-        raise AssertionError("%s: %d/%d outside tolerance (%d not finite), max finite err %.3g at |ref| %.3g; first at %s: got %r want %r" % (
-            name, bad.sum(), bad.size, wild(got, want).sum(), finite.max(), np.abs(want).flat[finite.argmax()],
-            tuple(int(i) for i in first), float(got[first]), float(want[first])))
 
 
 @pytest.mark.parametrize("case", ["composite", "composite_white"])
@@ -138,39 +102,6 @@ def test_color_lookup(hip):
     assert set(np.unique(m)) <= {0.0, 1.0}
 
 
-def _mlp_setup(case):
-    import zest_hip
-    inp = gc.build(case)
-    head = zest_hip.HEAD_NONE
-    if inp["sceneflow"] and inp["net_type"] == "v0":
-        head = zest_hip.HEAD_BLEND if inp["static"] else zest_hip.HEAD_DYNAMIC
-    use_feat = inp["use_mvs"] or inp["net_type"] == "v2"
-    shape = ()
-    if (inp["D"], inp["W"], tuple(inp["skips"])) != (8, 256, (4,)):
-        shape = (inp["D"], inp["W"], sum(1 << i for i in inp["skips"]))
-    desc = zest_hip.MlpDesc(inp["P"], inp["Fd"], gc.PE_DIR, int(use_feat),
-                            2 if inp["net_type"] == "v2" else 0, head, *shape)
-    state = {k: G(v) for k, v in inp["state"].items()}
-    return zest_hip, inp, desc, zest_hip.param_table(state, desc)
-
-
-def _mlp_module(inp):
-    """zest_networks.MVSNeRF of an MLP case (any depth / width / skips) with the case's weights, on the GPU."""
-    import zest_networks as networks
-    net = networks.MVSNeRF(D=inp["D"], W=inp["W"], skips=list(inp["skips"]), input_ch_pts=inp["P"],
-                           input_ch_views=gc.PE_DIR, input_ch_feat=inp["Fd"], net_type=inp["net_type"],
-                           sceneflow=inp["sceneflow"], static=inp["static"], use_mvs=inp["use_mvs"])
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in inp["state"].items()})
-    return net.cuda()
-
-
-# every MLP case runs in the fp32 kernel and the fp32 training path; the MFMA engine (bf16 / fp16 / split
-# fp16) is written for the shipped shape D=8, W=256, skips=[4]
-ALL_MLP_CASES = [c for c in gc.CASES if gc.CASES[c]["kind"] == "mlp"]
-SHAPE_MLP_CASES = [c for c in ALL_MLP_CASES if gc.mlp_shape(gc.CASES[c]["variant"]) != (8, 256, (4,))]
-MLP_CASES = [c for c in ALL_MLP_CASES if c not in SHAPE_MLP_CASES]
-
-
 @pytest.mark.parametrize("case", ALL_MLP_CASES)
 def test_mlp_f32(hip, case):
     zh, inp, desc, tab = _mlp_setup(case)
@@ -225,7 +156,6 @@ def test_mlp_view_counts(hip, V):
     """Feature operand layouts other than the fixtures' (V = 3, 4, 8): one k-tile up to 6 source
     views (all four lane groups used from V = 5 on), two k-tiles up to 14.  Checked against the
     oracle (pinned by the fixtures) on seeded inputs; both MFMA kernels."""
-    import torch
     import zest_hip as zh
     from oracle import zest_oracle as zo
     import oracle_run as orun
@@ -274,7 +204,6 @@ def test_channels_last_cache_hits_on_fresh_views(hip, monkeypatch):
 def test_forward_alpha_matches_reference(hip, case, exact, monkeypatch):
     """Renderer.forward_alpha / Renderer_linear.forward_alpha (reference networks.py:134-147, 266-280)
     against the reference's own outputs (fixture key `alpha_only`), both fp32-mode kernels."""
-    import zest_networks as networks
     monkeypatch.setenv("ZEST_FP32_EXACT", "1" if exact else "0")
     inp, gold = gc.build(case), gc.load_golden(case)
     net = _mlp_module(inp)

@@ -4,7 +4,7 @@ steps skipped on `found_inf` or a norm that is not finite, the step count kept o
 Every APPLIED step is judged from the state the optimiser itself had before it, by the float64 restatement of
 tests/optim_amp_cases.py (pinned to torch.optim.Adam under a real GradScaler in tests/test_optim_amp_cpu.py), within the
 three per-element bounds of tests/optim_cases.py, at the count of applied steps; every SKIPPED step must leave p, m, v bit
-for bit.  The tensors live in the sentinel-filled buffers of test_hip_optim.World; the memory either side of each is
+for bit.  The tensors live in the sentinel-filled buffers of optim_cases.World; the memory either side of each is
 checked after every step.
 """
 import copy
@@ -15,7 +15,8 @@ import torch
 
 import optim_amp_cases as ac
 import optim_cases as oc
-from test_hip_optim import DEV, MISALIGNED, World, _specs
+from gpu_cases import DEV
+from optim_cases import MISALIGNED, World, _specs
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +35,6 @@ def _optimizer(world, cls, lrs=None, **kw):
 
 def _scalar(x):
     return None if x is None else torch.tensor(float(x), dtype=torch.float32, device=DEV)
-
-
-def _judge(world, proto_t, old, got, flat, lr_of, coef, absent=(), label=""):
-    t = np.repeat(np.asarray(proto_t, dtype=np.float64), world.ns)
-    lr = np.repeat(np.asarray(lr_of, dtype=np.float64), world.ns)
-    present = ~np.isin(world.tensor_of, list(absent))
-    return oc.judge(got, old, flat, np.maximum(t, 1.0), lr, coef=coef, where=present, label=label)
 
 
 def amp_step(world, opt, proto, flat, scale=None, found_inf=None, absent=(), views=(), label=""):
@@ -70,7 +64,7 @@ def amp_step(world, opt, proto, flat, scale=None, found_inf=None, absent=(), vie
         for name, a, b in zip("pmv", old, got):
             assert np.array_equal(a.view(np.int32), b.view(np.int32)), "%s: a skipped step moved %s" % (label, name)
     else:
-        worst = _judge(world, ts, old, got, flat, lr_of, coef, absent, label)
+        worst = ac.judge(world, ts, old, got, flat, lr_of, coef, absent, label)
         present = ~np.isin(world.tensor_of, list(absent))
         for a, b in zip(old, got):
             assert np.array_equal(a[~present], b[~present])
@@ -309,7 +303,7 @@ def test_a_real_grad_scaler_steps_without_a_host_read(hip, monkeypatch, stage):
             if skip:
                 assert all(np.array_equal(a.view(np.int32), b.view(np.int32)) for a, b in zip(o, g)), "%s moved on the skipped step" % who
             else:
-                _judge(wa, ts, o, g, flat, lr_of, coef, label="%s step %d" % (who, step))
+                ac.judge(wa, ts, o, g, flat, lr_of, coef, label="%s step %d" % (who, step))
         wa.check_sentinels()
     print("scales %s; Tensor.item calls inside scaler.step: zest %d, torch %d" % (scales, items[0], items[1]))
     assert skipped == [4] and int(ours.skipped_steps) == 1

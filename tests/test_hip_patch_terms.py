@@ -3,7 +3,7 @@ depth patch, edge-aware depth smoothness) and the functions on top of them (zest
 get_disparity_smoothness, patch_terms, train_step_loss) against the reference's fixtures (tests/golden/patch_terms_*.npz)
 and, where the kernels can go wrong, against the float64 restatement in patch_cases.py.
 
-Bounds: values within test_hip_ops' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|): the
+Bounds: values within judges' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|): the
 bounds of test_hip_sf_ray_terms.py.  The inputs keep what stands under an |.| away from 0 by more than its fp32 rounding
 (patch_cases.inputs asserts it on the host before a comparison), so no element is excused; the tests on ties hold exact
 zeros there on purpose and compare with torch's sign(0) = 0."""
@@ -15,7 +15,8 @@ import pytest
 import torch
 
 import patch_cases as pc
-from test_hip_ops import G, close, ATOL
+from gpu_cases import G
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +54,7 @@ def _close_grad(got, want, name):
     if not np.abs(want).max() > 0:
         assert (got == 0).all(), name
         return
-    close(got, want, atol=ATOL * np.abs(want).max(), name=name)
+    scaled_close(got, want, name, ATOL, RTOL)
 
 
 def _against_restatement(inp, values, grads, name):

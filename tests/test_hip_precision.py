@@ -8,42 +8,16 @@ and every instantiation of the fused kernel (static feature tiles 0 / 2 / 4 x dy
 plain / with features) in each of them, the 'v2' net, and both pass shapes (ray ranges that finish
 every ray in the kernel, a ray spanning two passes carried in LDS; dense block shares + the combine launch).
 """
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 import torch
 
 import golden_cases as gc
 import oracle_run as orun
-from test_hip_ops import G, close, same_nonfinite, wild, ATOL, RTOL, MLP_CASES, _mlp_setup
-from test_hip_render import call_rendering, render_scene
+from gpu_cases import G, MAP_KEYS, MLP_CASES, TOL16, _mlp_setup, call_rendering, render_scene
+from judges import close, close_rays, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
-
-MAP_KEYS = ("rgb_map", "depth_map", "rgb_map_ref", "depth_map_ref", "rgb_map_ref_dy", "depth_map_ref_dy",
-            "weights_map_dd")
-# per-ray map tolerances of the 16-bit modes (absolute; colours / depths): measured worst cases on the
-# fixtures are 7e-3 / 3e-2 (bf16) and 6e-4 / 3e-3 (f16)
-TOL16 = {"bf16": (2e-2, 6e-2), "f16": (3e-3, 1e-2)}
-
-
-def close_rays(got, want, atol, rtol, name, max_bad=0):
-    """close() per ray, tolerating `max_bad` rays.  The reference gives the LAST sample of a ray a 1e10
-    interval (renderer.py:84): alpha there is 1 for any sigma > 0 and 0 otherwise, so a ray whose last
-    density is ~0 flips between 'saturated' and 'empty' under 16-bit operand noise - a discontinuity
-    of the reference's formula, not of the kernel."""
-    g = got.double().cpu().numpy() if torch.is_tensor(got) else np.asarray(got, np.float64)
-    w = np.asarray(want, np.float64)
-    assert g.shape == w.shape, (name, g.shape, w.shape)
-    # the flip moves a ray between two finite values: a NaN or an infinity on one side only is never excused
-    assert not wild(g, w).any(), "%s: %d entries non-finite on one side only" % (name, wild(g, w).sum())
-    same = same_nonfinite(g, w)
-    with np.errstate(invalid="ignore"):
-        err = np.where(same, 0.0, np.abs(g - w))
-    bad = (~(err <= atol + rtol * np.where(same, 0.0, np.abs(w)))).reshape(g.shape[0], -1).any(-1)
-    assert bad.sum() <= max_bad, "%s: %d rays outside %g + %g |ref| (max abs %.3g)" % (
-        name, bad.sum(), atol, rtol, err.max())
 
 
 # ------------------------------------------------------------------------- standalone MLP

@@ -87,7 +87,7 @@ def test_render_sharded_over_the_fused_renderer(rccl):
 def test_forward_val_gathers_once_per_image_over_rccl(rccl, monkeypatch):
     """The whole-image loop inside the group: one all-gather of the [H W, 13] maps, bit-equal to the image
     rendered without a group."""
-    import test_generators as tg
+    import package_cases as tg
     x = tg._batch(91)
     gen = tg._generator(tg._args(chunk=256, precision=16))
     calls = []

@@ -14,68 +14,12 @@ import torch
 
 import golden_cases as gc
 import oracle_run
-from test_hip_ops import G, close, ATOL, RTOL
+from gpu_cases import G, build_nets, call_rendering, render_scene
+from judges import close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 RENDER_CASES = [c for c in gc.CASES if gc.CASES[c]["kind"] == "render"]
 CHAIN2 = ("raw_pts_pp", "rgb_map_pp_dy")
-
-
-def build_nets(sc, net_type="v0"):
-    import zest_networks as networks
-    sf = sc["scene_flow"]
-    D, W, skips = sc.get("static_shape", (8, 256, (4,)))
-    ns = networks.MVSNeRF(D=D, W=W, input_ch_pts=gc.PE_PTS + sc.get("time_dim", 0), output_ch=4,
-                          input_ch_views=gc.PE_DIR, input_ch_feat=sc["feat_dim"], skips=list(skips), net_type=net_type,
-                          sceneflow=sf, static=True, use_mvs=sc["use_mvs"])
-    ns.load_state_dict({k: torch.from_numpy(v) for k, v in sc["state_static"].items()})
-    nd = None
-    if sf:
-        nd = networks.MVSNeRF(D=8, W=256, input_ch_pts=gc.PE_XYZT, output_ch=4,
-                              input_ch_views=gc.PE_DIR, input_ch_feat=24, skips=[4], net_type="v0",
-                              sceneflow=True, static=False, use_mvs=sc["use_mvs_dy"])
-        nd.load_state_dict({k: torch.from_numpy(v) for k, v in sc["state_dynamic"].items()})
-        nd = nd.to("cuda:0")
-    return ns.to("cuda:0"), nd
-
-
-def render_scene(sc, c, precision=32, monkeypatch=None, maps_only=False, dtype16="bf16", net_type="v0",
-                 fp32_exact=False, nets=None):
-    """renderer.rendering on a scene dict of golden_cases.render_inputs with the flags of case dict c.
-    nets: (static, dynamic) modules to reuse (their packed-weight caches with them)."""
-    import zest_networks as networks
-    import zest_renderer as renderer
-    sf = sc["scene_flow"]
-    ns, nd = nets if nets is not None else build_nets(sc, net_type)
-    args = SimpleNamespace(netchunk=1024, feat_dim=sc["feat_dim"], feat_dim_dy=24, img_downscale=1.0,
-                           use_color_volume=False, net_type=net_type, precision=precision,
-                           zest_maps_only=maps_only, zest_dtype16=dtype16, zest_fp32_exact=fp32_exact)
-    cam = {"w2cs": G(sc["w2cs"]), "intrinsics": G(sc["intrinsics"])}
-    dy = sf and sc["use_mvs_dy"]
-    nb_cam = {"w2cs": G(sc["nb_w2cs"]), "intrinsics": G(sc["nb_intrinsics"])} if dy else None
-    if sf and monkeypatch is not None:
-        queue = [G(sc["noise_static"])[None], G(sc["noise_blend"])[None]]
-        monkeypatch.setattr(renderer, "_draw_noise", lambda shape, device: queue.pop(0))
-    with torch.no_grad():
-        return renderer.rendering(
-            args, G(sc["rays_pts"]), G(sc["rays_ndc"]), G(sc["depth_candidates"]), G(sc["rays_dir"]),
-            volume_feature_static=G(sc["vol_static"]) if sc["use_mvs"] else None,
-            volume_feature_dynamic=G(sc["vol_dynamic"]) if dy else None,
-            imgs=G(sc["imgs"]) if sc["use_mvs"] else None,
-            neighbour_frames=G(sc["nb_imgs"]) if dy else None,
-            im_cam_mat=cam, nb_cam_mat=nb_cam, network_fn=ns, network_fn_dy=nd,
-            embedding_pts=networks.Embedding(3, 10), embedding_xyzt=networks.Embedding(4, 10),
-            embedding_dir=networks.Embedding(3, 4),
-            chain_bwd=c.get("chain_bwd", False), chain_5frames=c.get("chain_5frames", False),
-            ref_frame_idx=gc.REF_FRAME_IDX, num_frames=gc.NUM_FRAMES,
-            white_bkgd=c.get("white_bkgd", False), scene_flow=sf, val=c.get("val", False),
-            raw_noise_std=c.get("raw_noise_std", 0),
-            time_codes=G(sc["time_codes"]) if sc.get("time_dim", 0) else None)
-
-
-def call_rendering(case, precision=32, monkeypatch=None, maps_only=False, dtype16="bf16", fp32_exact=False):
-    return render_scene(gc.build(case), gc.CASES[case], precision, monkeypatch, maps_only, dtype16,
-                        fp32_exact=fp32_exact)
 
 
 @pytest.mark.parametrize("exact", [False, True], ids=["f16x3", "exact"])

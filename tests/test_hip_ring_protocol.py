@@ -25,10 +25,9 @@ import torch
 
 import golden_cases as gc
 import oracle_run as orun
-from test_hip_ops import G, close, ATOL, RTOL, _mlp_setup
-from test_hip_precision import MAP_KEYS, TOL16, close_rays
-from test_hip_render import build_nets, render_scene
-from test_hip_train16 import oracle_grads, rel
+from gpu_cases import G, MAP_KEYS, TOL16, _mlp_setup, build_nets, render_scene
+from judges import close, close_rays, ATOL, RTOL, l2_ratio as rel
+from train16_cases import oracle_grads
 
 pytestmark = pytest.mark.gpu
 

@@ -2,7 +2,7 @@
 reference's fixtures (its fp32 values and its own autograd gradients, tests/golden/sf_losses_*.npz) and, at the
 shapes where the kernel's lane chunks begin and end, against the float64 restatement in sf_loss_cases.py.
 
-Bounds: values within test_hip_ops' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|), as
+Bounds: values within judges' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|), as
 test_projection_from_ndc_matches_reference does.  The inputs keep every neighbour difference of the spatial term
 away from 0 by more than its fp32 rounding (sf_loss_cases.margins, asserted on the host before a comparison), so the
 gradient of |.| needs no allowance."""
@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import sf_loss_cases as sc
-from test_hip_ops import G, close, ATOL, RTOL
+from gpu_cases import G
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,7 @@ def _close_grads(p, want, name):
         if leaf.grad is None:
             assert not np.abs(w).max() > 0, (name, t)
             continue
-        close(leaf.grad.reshape(w.shape), w, atol=ATOL * np.abs(w).max(), name="%s: d / d %s" % (name, t))
+        scaled_close(leaf.grad.reshape(w.shape), w, "%s: d / d %s" % (name, t), ATOL, RTOL)
 
 
 @pytest.mark.parametrize("R,S", sc.CASES)
@@ -124,7 +125,7 @@ def test_chunk_boundaries_against_the_restatement(hip, R, S):
             g = bufs[k].cpu().numpy()
             assert not np.isnan(g).any(), (names, t)
             assert (g[:, reach[t]:] == 0).all(), (names, t)
-            close(bufs[k], want_g[t], atol=ATOL * np.abs(want_g[t]).max(), name="%s: d / d %s" % (names, t))
+            scaled_close(bufs[k], want_g[t], "%s: d / d %s" % (names, t), ATOL, RTOL)
 
 
 def test_unread_tensor_with_a_gradient_buffer_gets_zeros(hip):
@@ -151,7 +152,7 @@ def test_autograd_paths(hip):
     sp, st = sc.training_set(True)
     _, want_g = sc.combine(values, grads, (R, S, 3), dict({n: C_SP for n in sp}, **{n: C_ST for n in st}))
     assert ref.grad is None and prev.grad is None and pp.grad is None
-    close(post.grad, want_g["post"], atol=ATOL * np.abs(want_g["post"]).max(), name="d / d post alone")
+    scaled_close(post.grad, want_g["post"], "d / d post alone", ATOL, RTOL)
     # no graph: the forward runs and returns the values
     with torch.no_grad():
         t2, sp2, st2 = L.scene_flow_regularisers(ref, post, prev, pp, True, sc.H, sc.W, sc.F, w_sp=C_SP, w_st=C_ST)

@@ -3,7 +3,7 @@ image error, optical-flow error, whitened depth prior) and the whole step loss o
 (zest_losses.train_sf_step_loss, ray_terms="hip" and "torch") against the reference's fixtures
 (tests/golden/sf_step_*.npz) and, where the kernels can go wrong, against the float64 restatement in sf_step_cases.py.
 
-Bounds: values within test_hip_ops' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|).
+Bounds: values within judges' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|).
 The inputs keep what stands under an |.| away from 0 by more than its fp32 rounding and hold one element at each median
 (sf_ray_cases.inputs asserts it on the host before a comparison), so no element is excused."""
 import types
@@ -14,7 +14,8 @@ import torch
 
 import sf_ray_cases as rc
 import sf_step_cases as ss
-from test_hip_ops import G, close, ATOL
+from gpu_cases import G
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -41,22 +42,6 @@ def _leaves(inp, requires=rc.GRADS, shape=None, dtype=torch.float32, five=True, 
 def _call(p, late, w_flow=COEFF["flow_fwd"], w_depth=COEFF["depth"]):
     import zest_losses as L
     return L.scene_flow_ray_terms(*[p[k] for k in rc.TENSORS], late, w_flow=w_flow, w_depth=w_depth)
-
-
-def _close_grads(p, want, name):
-    for k in rc.GRADS:
-        leaf = p[k]
-        if leaf is None:
-            continue
-        if not leaf.requires_grad:
-            assert leaf.grad is None, (name, k)
-            continue
-        w = want[k]
-        assert leaf.grad is not None and leaf.grad.shape == leaf.shape and leaf.grad.dtype == leaf.dtype, (name, k)
-        if not np.abs(w).max() > 0:
-            assert (leaf.grad == 0).all(), (name, k)
-            continue
-        close(leaf.grad.reshape(w.shape), w, atol=ATOL * np.abs(w).max(), name="%s: d / d %s" % (name, k))
 
 
 def _close_values(got, values, coeff, name):
@@ -91,7 +76,7 @@ def test_per_ray_terms_match_the_reference(hip, R, S, config):
                 assert k == "rgb_map_pp_dy" and p[k] is None
                 continue
             w = gold[key]
-            close(p[k].grad, w, atol=ATOL * np.abs(w).max(), name="d / d " + k)
+            scaled_close(p[k].grad, w, "d / d " + k, ATOL, RTOL)
 
 
 @pytest.mark.parametrize("five", (True, False))
@@ -109,7 +94,7 @@ def test_sizes_against_the_restatement(hip, R, late, five):
     got = _call(p, late)
     got[0].backward()
     _close_values(got, values, COEFF, "R=%d" % R)
-    _close_grads(p, rc.combine(values, grads, inp, COEFF)[1], "R=%d late=%s five=%s" % (R, late, five))
+    ss.close_grads(p, rc.combine(values, grads, inp, COEFF)[1], "R=%d late=%s five=%s" % (R, late, five), rc.GRADS)
 
 
 def _masks():
@@ -153,7 +138,7 @@ def test_each_term_alone_and_subsets(hip, R, late, five):
                 assert (bufs[i] == 0).all(), (names, k)
                 continue
             w = want_g[k][0]
-            close(bufs[i], w, atol=ATOL * np.abs(w).max(), name="%s: d / d %s" % (names, k))
+            scaled_close(bufs[i], w, "%s: d / d %s" % (names, k), ATOL, RTOL)
 
 
 @pytest.mark.parametrize("frame_t", (0, 5, ss.TOTAL_FRAMES - 1))
@@ -166,7 +151,7 @@ def test_first_last_and_middle_frame(hip, frame_t):
     got = _call(p, late)
     got[0].backward()
     _close_values(got, values, coeff, "frame %d" % frame_t)
-    _close_grads(p, rc.combine(values, grads, inp, coeff)[1], "frame %d" % frame_t)
+    ss.close_grads(p, rc.combine(values, grads, inp, coeff)[1], "frame %d" % frame_t, rc.GRADS)
 
 
 def test_autograd_paths(hip):
@@ -177,7 +162,7 @@ def test_autograd_paths(hip):
     for only in ("prob_map_post", "depth_map_ref_dy", "flow_bwd", "rgb_map_pp_dy"):
         p = _leaves(inp, requires=(only,))
         _call(p, late)[0].backward()
-        _close_grads(p, want_g, "only " + only)
+        ss.close_grads(p, want_g, "only " + only, rc.GRADS)
     # no graph: the forward launch alone, the same values bit for bit
     p = _leaves(inp)
     ref = _call(p, late)
@@ -197,7 +182,7 @@ def test_autograd_paths(hip):
     # the upstream scalar multiplies the gradients
     p = _leaves(inp)
     (2.5 * _call(p, late)[0]).backward()
-    _close_grads(p, {k: 2.5 * g for k, g in want_g.items()}, "upstream 2.5")
+    ss.close_grads(p, {k: 2.5 * g for k, g in want_g.items()}, "upstream 2.5", rc.GRADS)
 
 
 def test_no_backward_launch_without_a_gradient(hip, monkeypatch):
@@ -224,7 +209,7 @@ def test_leading_dimensions_and_other_dtypes(hip):
         got = _call(p, late)
         got[0].backward()
         _close_values(got, values, COEFF, str(shape))
-        _close_grads(p, want_g, str(shape))
+        ss.close_grads(p, want_g, str(shape), rc.GRADS)
     views = {}
     for k in rc.TENSORS:
         t = G(inp[k])
@@ -235,7 +220,7 @@ def test_leading_dimensions_and_other_dtypes(hip):
     got = _call(views, late)
     got[0].backward()
     _close_values(got, values, COEFF, "strided views")
-    _close_grads(views, want_g, "strided views")
+    ss.close_grads(views, want_g, "strided views", rc.GRADS)
 
 
 @pytest.mark.parametrize("R,S", ((8, 4), (64, 4)))
@@ -262,7 +247,7 @@ def test_whole_step_both_ways_against_the_restatement(hip, R, S, config):
             if grads64[k] is None:
                 assert r[k].grad is None and k == "rgb_map_pp_dy", (way, k)
                 continue
-            close(r[k].grad, grads64[k], atol=ATOL * np.abs(grads64[k]).max(), name="%s d / d %s" % (way, k))
+            scaled_close(r[k].grad, grads64[k], "%s d / d %s" % (way, k), ATOL, RTOL)
 
 
 def test_a_custom_criterion_takes_the_torch_path(hip, monkeypatch):

@@ -3,7 +3,7 @@
 tests/golden/sf_step_*.npz) and, at the shapes where the kernel's lane chunks begin and end, against the float64
 restatement in sf_step_cases.py.
 
-Bounds: values within test_hip_ops' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|).
+Bounds: values within judges' ATOL + RTOL |want|; gradients within ATOL * max|want| absolute (+ RTOL |want|).
 The inputs keep everything under an |.| away from 0 by more than its fp32 rounding (sf_step_cases.margins, asserted
 on the host before a comparison), so no element is excused."""
 import functools
@@ -14,7 +14,8 @@ import pytest
 import torch
 
 import sf_step_cases as ss
-from test_hip_ops import G, close, ATOL, RTOL
+from gpu_cases import G
+from judges import close, scaled_close, ATOL, RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -75,19 +76,6 @@ def _leaves(inp, requires=ss.SAMPLE_TENSORS, shape=None, dtype=torch.float32):
     return out
 
 
-def _close_grads(p, want, name):
-    for k, leaf in p.items():
-        if not leaf.requires_grad:
-            assert leaf.grad is None, (name, k)
-            continue
-        w = want[k]
-        assert leaf.grad is not None and leaf.grad.shape == leaf.shape, (name, k)
-        if not np.abs(w).max() > 0:
-            assert (leaf.grad == 0).all(), (name, k)
-            continue
-        close(leaf.grad.reshape(w.shape), w, atol=ATOL * np.abs(w).max(), name="%s: d / d %s" % (name, k))
-
-
 def _call(p, coeff):
     import zest_losses as L
     return L.scene_flow_sample_terms(*[p[k] for k in ss.SAMPLE_TENSORS], *[coeff.get(t, 0.0) for t in TERM_ORDER])
@@ -108,7 +96,7 @@ def test_per_sample_terms_match_the_reference(hip, R, S, which):
     for t, v in zip(TERM_ORDER, four):
         close(v.reshape(1), np.reshape(values[t], 1), name=t)
     close(total.detach().reshape(1), np.reshape(want, 1), name="total")
-    _close_grads(p, want_g, which)
+    ss.close_grads(p, want_g, which)
 
 
 @pytest.mark.parametrize("R,S", ss.CASES)
@@ -134,7 +122,7 @@ def test_whole_step_matches_the_reference(hip, R, S, config):
             assert r[k].grad is None and k == "rgb_map_pp_dy", k
             continue
         w = gold[key]
-        close(r[k].grad, w, atol=ATOL * np.abs(w).max(), name="d / d " + k)
+        scaled_close(r[k].grad, w, "d / d " + k, ATOL, RTOL)
 
 
 @pytest.mark.parametrize("R,S", ss.BOUNDARY + ss.PARTIAL_WORKGROUP)
@@ -172,7 +160,7 @@ def test_chunk_boundaries_against_the_restatement(hip, R, S):
                 assert (bufs[i] == 0).all(), (names, k)
                 continue
             w = want_g[k][0]
-            close(bufs[i], w, atol=ATOL * np.abs(w).max(), name="%s: d / d %s" % (names, k))
+            scaled_close(bufs[i], w, "%s: d / d %s" % (names, k), ATOL, RTOL)
 
 
 def test_autograd_paths(hip):
@@ -184,7 +172,7 @@ def test_autograd_paths(hip):
         p = _leaves(inp, requires=(only,))
         total, *_ = _call(p, COEFF)
         total.backward()
-        _close_grads(p, want_g, "only " + only)
+        ss.close_grads(p, want_g, "only " + only)
     # no graph: the forward launch alone, the same values bit for bit
     p = _leaves(inp)
     ref = _call(p, COEFF)
@@ -204,7 +192,7 @@ def test_autograd_paths(hip):
     # the upstream scalar multiplies the gradients
     p = _leaves(inp)
     (2.5 * _call(p, COEFF)[0]).backward()
-    _close_grads(p, {k: 2.5 * g for k, g in want_g.items()}, "upstream 2.5")
+    ss.close_grads(p, {k: 2.5 * g for k, g in want_g.items()}, "upstream 2.5")
 
 
 def test_leading_dimensions_and_other_dtypes(hip):
@@ -218,7 +206,7 @@ def test_leading_dimensions_and_other_dtypes(hip):
         total.backward()
         close(total.detach().reshape(1), np.reshape(want, 1), name=str(shape))
         assert all(p[k].grad.dtype == dtype for k in p)
-        _close_grads(p, want_g, str(shape))
+        ss.close_grads(p, want_g, str(shape))
     wide = {k: torch.zeros(G(inp[k]).shape[:3] + (2 * inp[k][0, 0, 0].size,), device="cuda:0") for k in ss.SAMPLE_TENSORS}
     views = {}
     for k in ss.SAMPLE_TENSORS:

@@ -6,50 +6,15 @@ import numpy as np
 import pytest
 import torch
 
+import backward_cases as bc
 import golden_cases as gc
 import oracle_run as orun
-from test_hip_ops import G, _mlp_setup
+from gpu_cases import G, _mlp_setup
+from judges import l2_ratio as rel
+from train16_cases import _Bf16Operands, oracle_grads
 
 pytestmark = pytest.mark.gpu
 V0_CASES = ["mlp_static_mvs20", "mlp_static_nomvs", "mlp_static_sf_mvs40", "mlp_dynamic_mvs24", "mlp_dynamic_nomvs"]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.sqrt(((a - b) ** 2).sum()) / (np.sqrt((b ** 2).sum()) + 1e-30))
-
-
-class _Bf16Operands:
-    """The oracle's MLP with every GEMM operand rounded to bf16 (straight-through: identity in backward),
-    fp32/fp64 accumulation and epilogues - the arithmetic of the engine.  ReLU is not differentiable at 0:
-    a unit whose pre-activation is within bf16 noise of 0 is 'on' in one evaluation and 'off' in another, and
-    each such flip moves a layer's gradient by ~1/sqrt(active units), i.e. ~10 % of its norm per 1 % of flipped
-    units.  The gradient check therefore differentiates the SAME rounded network (same masks) instead of the
-    fp64 one; the forward check below still compares with the un-rounded oracle."""
-
-    def __enter__(self):
-        import torch.nn.functional as F
-        self.F, self.real = F, F.linear
-        r = lambda t: t + (t.to(torch.bfloat16).to(t.dtype) - t).detach()
-        F.linear = lambda x, w, b=None: self.real(r(x), r(w), b)
-        return self
-
-    def __exit__(self, *a):
-        self.F.linear = self.real
-
-
-def oracle_grads(inp, x, gw, bf16_operands=True):
-    from oracle import zest_oracle as zo
-    state = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in inp["state"].items()}
-    xt = torch.from_numpy(x).double().requires_grad_(True)
-    spec = orun.spec_of(inp["P"], inp["Fd"], inp["sceneflow"], inp["static"], inp["use_mvs"], inp["net_type"])
-    if bf16_operands:
-        with _Bf16Operands():
-            y = zo.mlp_forward(state, xt, spec)
-    else:
-        y = zo.mlp_forward(state, xt, spec)
-    (y * torch.from_numpy(gw).double()).sum().backward()
-    return y.detach().numpy(), xt.grad.numpy(), {k: (v.grad.numpy() if v.grad is not None else None) for k, v in state.items()}
 
 
 @pytest.mark.parametrize("M", [64, 300, 1, 31])       # whole blocks, ragged, fewer samples than one block of 32
@@ -102,34 +67,10 @@ def test_rendering_trains_in_bf16_mode(hip, case):
     differ by 1-4 % there, tests/test_hip_backward.py), so the per-ray colour maps are compared (3e-2) and the
     gradients of the static net and volume (not behind the chain) must stay aligned (cosine > 0.6; measured 0.79 - 0.99), the dynamic ones
     finite and non-zero."""
-    import zest_networks as networks
-    import zest_renderer as renderer
-    from types import SimpleNamespace
-    from test_hip_render import build_nets
-    c, sc = gc.CASES[case], gc.build(case)
-    sf = sc["scene_flow"]
-    W = None
+    sf = gc.build(case)["scene_flow"]
     res = {}
     for prec in (32, 16):
-        ns, nd = build_nets(sc)
-        vol_s = G(sc["vol_static"]).requires_grad_(True)
-        vol_d = G(sc["vol_dynamic"]).requires_grad_(True) if sf else None
-        args = SimpleNamespace(netchunk=1024, feat_dim=sc["feat_dim"], feat_dim_dy=24, img_downscale=1.0,
-                               use_color_volume=False, net_type="v0", precision=prec)
-        cam = {"w2cs": G(sc["w2cs"]), "intrinsics": G(sc["intrinsics"])}
-        nb_cam = {"w2cs": G(sc["nb_w2cs"]), "intrinsics": G(sc["nb_intrinsics"])} if sf else None
-        ret = renderer.rendering(
-            args, G(sc["rays_pts"]), G(sc["rays_ndc"]), G(sc["depth_candidates"]), G(sc["rays_dir"]),
-            volume_feature_static=vol_s, volume_feature_dynamic=vol_d, imgs=G(sc["imgs"]),
-            neighbour_frames=G(sc["nb_imgs"]) if sf else None, im_cam_mat=cam, nb_cam_mat=nb_cam, network_fn=ns,
-            network_fn_dy=nd, embedding_pts=networks.Embedding(3, 10), embedding_xyzt=networks.Embedding(4, 10),
-            embedding_dir=networks.Embedding(3, 4), chain_5frames=c.get("chain_5frames", False),
-            ref_frame_idx=gc.REF_FRAME_IDX, num_frames=gc.NUM_FRAMES, white_bkgd=c.get("white_bkgd", False),
-            scene_flow=sf, val=False)
-        if W is None:
-            W = gc.loss_weights(c["seed"], {k: tuple(v.shape[1:]) for k, v in ret.items() if v is not None})
-        loss = sum((G(W[k]) * ret[k][0]).sum() for k in W)
-        loss.backward()
+        ret, loss, ns, nd, _, vol_s, vol_d = bc.train_render(case, prec)
         grads = {"vol_static": vol_s.grad}
         if sf:
             grads["vol_dynamic"] = vol_d.grad
@@ -165,33 +106,9 @@ def test_rendering_trains_in_bf16_mode(hip, case):
 def _hip_render_grads(case, precision):
     """Train-mode rendering() of a gradient case on the GPU -> (loss, {leaf name: gradient ndarray}) with the leaf
     naming of oracle_run.oracle_render_grads."""
-    import zest_networks as networks
-    import zest_renderer as renderer
-    from types import SimpleNamespace
-    from test_hip_render import build_nets
-    c, sc = gc.CASES[case], gc.build(case)
-    sf = sc["scene_flow"]
-    ns, nd = build_nets(sc)
-    dy = sf and sc["use_mvs_dy"]
-    vol_s = G(sc["vol_static"]).requires_grad_(True)
-    vol_d = G(sc["vol_dynamic"]).requires_grad_(True) if dy else None
-    args = SimpleNamespace(netchunk=1024, feat_dim=sc["feat_dim"], feat_dim_dy=24, img_downscale=1.0,
-                           use_color_volume=False, net_type="v0", precision=precision)
-    cam = {"w2cs": G(sc["w2cs"]), "intrinsics": G(sc["intrinsics"])}
-    nb_cam = {"w2cs": G(sc["nb_w2cs"]), "intrinsics": G(sc["nb_intrinsics"])} if dy else None
-    ret = renderer.rendering(
-        args, G(sc["rays_pts"]), G(sc["rays_ndc"]), G(sc["depth_candidates"]), G(sc["rays_dir"]),
-        volume_feature_static=vol_s, volume_feature_dynamic=vol_d, imgs=G(sc["imgs"]),
-        neighbour_frames=G(sc["nb_imgs"]) if dy else None, im_cam_mat=cam, nb_cam_mat=nb_cam, network_fn=ns,
-        network_fn_dy=nd, embedding_pts=networks.Embedding(3, 10), embedding_xyzt=networks.Embedding(4, 10),
-        embedding_dir=networks.Embedding(3, 4), chain_bwd=c.get("chain_bwd", False),
-        chain_5frames=c.get("chain_5frames", False), ref_frame_idx=gc.REF_FRAME_IDX, num_frames=gc.NUM_FRAMES,
-        white_bkgd=c.get("white_bkgd", False), scene_flow=sf, val=False)
-    W = gc.loss_weights(c["seed"], {k: tuple(v.shape[1:]) for k, v in ret.items() if v is not None})
-    loss = sum((G(W[k]) * ret[k][0]).sum() for k in W)
-    loss.backward()
+    _, loss, ns, nd, _, vol_s, vol_d = bc.train_render(case, precision)
     got = {"vol_static": vol_s.grad[0]}
-    if dy:
+    if vol_d is not None:
         got["vol_dynamic"] = vol_d.grad[0]
     for tag, net in (("static", ns), ("dynamic", nd)):
         if net is not None:

@@ -18,8 +18,8 @@ import torch
 
 import golden_cases as gc
 import train16_cases as tc
-from test_hip_ops import G
-from test_hip_train16 import rel
+from gpu_cases import G
+from judges import l2_ratio as rel
 
 pytestmark = pytest.mark.gpu
 B = tc.BLOCK
@@ -388,15 +388,14 @@ def test_stages_one_by_one_equal_all_at_once(hip):
 def test_train16_dynamic_net_with_40_features_matches_the_oracle(hip, M):
     """Kernel instance (6 point units, 4 feature units): the dynamic net on more than 32 feature channels, with the
     parametrisation and bounds of test_train16_forward_and_backward_match_the_oracle."""
-    from test_hip_train16 import oracle_grads
     case = "mlp_dynamic_mvs40"
     n = net(case)
     inp, desc, zh = n.inp, n.desc, n.zh
     rng = gc.zs.rng(900 + M)
     x = rng.uniform(-1, 1, size=(M, desc.in_ch)).astype(np.float32)
     gw = rng.standard_normal((M, desc.out_ch)).astype(np.float32)
-    y_ref, gx_ref, gp_ref = oracle_grads(inp, x, gw)
-    y64, _, _ = oracle_grads(inp, x, gw, bf16_operands=False)
+    y_ref, gx_ref, gp_ref = tc.oracle_grads(inp, x, gw)
+    y64, _, _ = tc.oracle_grads(inp, x, gw, bf16_operands=False)
     out, stash = n.fwd(G(x))
     assert rel(out.cpu().numpy(), y64) < 2e-2 and rel(out.cpu().numpy(), y_ref) < 2e-3
     g_x, grads, _ = n.bwd(G(x), stash, out, G(gw))

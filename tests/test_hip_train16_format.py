@@ -29,8 +29,7 @@ import torch
 import engine_format_cases as ef
 import train16_cases as tc
 import train16_format_cases as tf
-from test_hip_engine_format import _desc_and_table
-from test_hip_ops import G
+from gpu_cases import G, _mlp_table
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +39,7 @@ def _net(case, exact_M=0):
     """(inp, desc, parameter table, packed forward stream, packed backward stream).  Cached: do not modify."""
     import zest_hip as zh
     inp = tf.exact_case(case, exact_M)[0] if exact_M else tc.net_inputs(case)
-    desc, tab = _desc_and_table(zh, inp)
+    desc, tab = _mlp_table(zh, inp)
     return inp, desc, tab, zh.mlp_pack(desc, zh.PREC_BF16, tab), zh.mlp_train16_pack_bwd(desc, tab)
 
 

@@ -4,15 +4,15 @@ inputs, and the fp32 training path with the switch on.
 Every operand lives in a buffer as wide as its leading dimension whose padding is NaN (a read past a row poisons the
 result), every output buffer is pre-filled with a sentinel that must survive outside [rows, cols] of the result."""
 import warnings
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import backward_cases as bc
 import golden_cases as gc
 import train_gemm_cases as tg
-from test_hip_ops import ALL_MLP_CASES, G, _mlp_setup
+from gpu_cases import ALL_MLP_CASES, G, _mlp_module, _mlp_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -52,24 +52,6 @@ def run_both(zh, op, a, b, lda, ldb, ldc, c0=None, c_off=0, b_off=0):
     return out
 
 
-def check_bound(zh, op, a, b, got, c0=None, name=""):
-    """|got - ref64| <= c sum |a||b| per entry, c = max(4 r_lib, 2^-21) with r_lib measured here.  With beta = 1 the
-    old value of c is one more term of the sum (c0 . 1), in the reference and in the magnitude."""
-    A, B = tg.as_ik_jk(op, a, b)
-    ref, mag = tg.ref64(A, B)
-    if c0 is not None:
-        ref, mag = ref + c0, mag + np.abs(c0)
-    assert np.all(np.isfinite(ref)) and np.all(np.isfinite(mag)), name
-    # the library's error sets the bound: a non-finite library result would make it infinite, or NaN
-    assert np.all(np.isfinite(got[zh.GEMM_LIBRARY])), "%s: the library result is not finite" % name
-    assert np.all(np.isfinite(got[zh.GEMM_SPLIT_BF16])), name
-    r_lib, r_split = tg.ratio(got[zh.GEMM_LIBRARY], ref, mag), tg.ratio(got[zh.GEMM_SPLIT_BF16], ref, mag)
-    c = tg.bound_factor(r_lib)
-    print("%s: library %.3g  split %.3g  bound %.3g" % (name, r_lib, r_split, c))
-    assert np.isfinite(c), "%s: bound %r from the library's %r" % (name, c, r_lib)
-    assert r_split <= c, "%s: split %.3g > bound %.3g (library %.3g)" % (name, r_split, c, r_lib)
-
-
 @pytest.mark.parametrize("cnt", [1, 16])
 @pytest.mark.parametrize("op", list(OPS))
 def test_isolation_case_on_the_device(hip, op, cnt):
@@ -104,7 +86,7 @@ def test_ragged_sizes_of_the_call_sites(hip, op, shape):
         for beta in (0, 1):
             c0 = (rng.standard_normal((rc, cc)) * np.abs(a).mean()).astype(np.float32) if beta else None
             got = run_both(zh, OPS[op], a, b, lda, ldb, ldc, c0)
-            check_bound(zh, OPS[op], a, b, got, c0, "%s M=%d beta=%d %s" % (op, M, beta, shape))
+            tg.check_bound(zh, OPS[op], a, b, got, c0, "%s M=%d beta=%d %s" % (op, M, beta, shape))
 
 
 @pytest.mark.parametrize("cols,ld,off", [(3, 16, 3), (6, 16, 4)])
@@ -119,7 +101,7 @@ def test_output_sub_blocks_in_place(hip, cols, ld, off):
         for beta in (0, 1):
             c0 = rng.standard_normal((M, cols)).astype(np.float32) if beta else None
             got = run_both(zh, tg.OP_NT, a, b, K, K, ld, c0, c_off=off)
-            check_bound(zh, tg.OP_NT, a, b, got, c0, "NT into +%d of ld %d, M=%d beta=%d" % (off, ld, M, beta))
+            tg.check_bound(zh, tg.OP_NT, a, b, got, c0, "NT into +%d of ld %d, M=%d beta=%d" % (off, ld, M, beta))
     # an output block at +63 of a 319-wide buffer (rows that start off a 16-byte boundary), data gradient and forward
     for op, a in ((tg.OP_NN, tg.gradient_like(rng, 129, cols)), (tg.OP_NT, np.maximum(rng.standard_normal((129, 256)), 0).astype(np.float32))):
         w = (rng.standard_normal((cols, 256)) / 16).astype(np.float32)
@@ -127,7 +109,7 @@ def test_output_sub_blocks_in_place(hip, cols, ld, off):
         for beta in (0, 1):
             c0 = (rng.standard_normal(rc) * np.abs(a).mean()).astype(np.float32) if beta else None
             got = run_both(zh, op, a, w, a.shape[1], 256, 319, c0, c_off=63)
-            check_bound(zh, op, a, w, got, c0, "op %d into +63 of ld 319, beta=%d" % (op, beta))
+            tg.check_bound(zh, op, a, w, got, c0, "op %d into +63 of ld 319, beta=%d" % (op, beta))
     # the data gradient reads the same sub-block (dhp + off) and the skip layer's weights at w + 63, ld 319
     a = tg.gradient_like(rng, 129, cols)
     _, av = padded(a, ld, off)
@@ -136,7 +118,7 @@ def test_output_sub_blocks_in_place(hip, cols, ld, off):
     got = {}
     for kind in (zh.GEMM_LIBRARY, zh.GEMM_SPLIT_BF16):
         got[kind] = zh.train_gemm(kind, tg.OP_NN, av, wv).cpu().numpy()
-    check_bound(zh, tg.OP_NN, a, w, got, None, "NN from +%d of ld %d and +63 of ld 319" % (off, ld))
+    tg.check_bound(zh, tg.OP_NN, a, w, got, None, "NN from +%d of ld %d and +63 of ld 319" % (off, ld))
 
 
 @pytest.mark.parametrize("shape", tg.TN_SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -149,7 +131,7 @@ def test_weight_gradient_over_chunks(hip, shape):
         a = tg.gradient_like(rng, M, N)
         b = np.maximum(rng.standard_normal((M, K)), 0).astype(np.float32)
         got = run_both(zh, tg.OP_TN, a, b, lda, ldb, ldc)
-        check_bound(zh, tg.OP_TN, a, b, got, None, "TN M=%d %s" % (M, shape))
+        tg.check_bound(zh, tg.OP_TN, a, b, got, None, "TN M=%d %s" % (M, shape))
 
 
 def test_weight_gradient_into_the_skip_layers_block(hip):
@@ -159,7 +141,7 @@ def test_weight_gradient_into_the_skip_layers_block(hip):
     M = zh.train_gemm_chunk_rows() + 129
     a, b = tg.gradient_like(rng, M, 256), np.maximum(rng.standard_normal((M, 256)), 0).astype(np.float32)
     got = run_both(zh, tg.OP_TN, a, b, 256, 256, 319, c_off=63)
-    check_bound(zh, tg.OP_TN, a, b, got, None, "TN into +63 of ld 319")
+    tg.check_bound(zh, tg.OP_TN, a, b, got, None, "TN into +63 of ld 319")
 
 
 @pytest.mark.parametrize("op", list(OPS))
@@ -195,10 +177,9 @@ def test_mlp_train_forward_backward_split(hip, case, monkeypatch):
     """test_mlp_train_forward_backward with the switch on (its own body, its own tolerances), then two identical
     backward calls: weight and data gradients bit for bit."""
     import zest_hip as zh
-    from test_hip_backward import test_mlp_train_forward_backward
     monkeypatch.setenv("ZEST_TRAIN_GEMM", "split")
     spy = _Spy(monkeypatch)
-    test_mlp_train_forward_backward(hip, case)
+    bc.mlp_train_forward_backward(case)
     assert spy.seen == [zh.GEMM_SPLIT_BF16] * 2
     monkeypatch.undo()
     _, inp, desc, tab = _mlp_setup(case)
@@ -223,7 +204,6 @@ def test_rendering_training_gradients_split(hip, case, monkeypatch):
     """test_rendering_training_gradients with args.zest_train_gemm = "split": its own body and tolerances."""
     import zest_hip as zh
     import zest_renderer as renderer
-    from test_hip_backward import test_rendering_training_gradients
     real = renderer.rendering
 
     def rendering(args, *a, **kw):
@@ -232,30 +212,13 @@ def test_rendering_training_gradients_split(hip, case, monkeypatch):
     monkeypatch.delenv("ZEST_TRAIN_GEMM", raising=False)
     monkeypatch.setattr(renderer, "rendering", rendering)
     spy = _Spy(monkeypatch)
-    test_rendering_training_gradients(hip, case)
+    bc.rendering_training_gradients(case)
     assert len(spy.seen) >= 2 and set(spy.seen) == {zh.GEMM_SPLIT_BF16}
 
 
 def _render_static(precision, **extra):
     """train-mode rendering() of the static gradient case -> (outputs, parameter gradients)"""
-    import zest_networks as networks
-    import zest_renderer as renderer
-    from test_hip_render import build_nets
-    case = "grad_static"
-    c, sc = gc.CASES[case], gc.build(case)
-    ns, _ = build_nets(sc)
-    vol_s = G(sc["vol_static"]).requires_grad_(True)
-    args = SimpleNamespace(netchunk=1024, feat_dim=sc["feat_dim"], feat_dim_dy=24, img_downscale=1.0,
-                           use_color_volume=False, net_type="v0", precision=precision, **extra)
-    ret = renderer.rendering(
-        args, G(sc["rays_pts"]), G(sc["rays_ndc"]), G(sc["depth_candidates"]), G(sc["rays_dir"]),
-        volume_feature_static=vol_s, volume_feature_dynamic=None, imgs=G(sc["imgs"]), neighbour_frames=None,
-        im_cam_mat={"w2cs": G(sc["w2cs"]), "intrinsics": G(sc["intrinsics"])}, nb_cam_mat=None, network_fn=ns,
-        network_fn_dy=None, embedding_pts=networks.Embedding(3, 10), embedding_xyzt=networks.Embedding(4, 10),
-        embedding_dir=networks.Embedding(3, 4), ref_frame_idx=gc.REF_FRAME_IDX, num_frames=gc.NUM_FRAMES,
-        white_bkgd=c.get("white_bkgd", False), scene_flow=False, val=False)
-    W = gc.loss_weights(c["seed"], {k: tuple(v.shape[1:]) for k, v in ret.items() if v is not None})
-    sum((G(W[k]) * ret[k][0]).sum() for k in W).backward()
+    ret, _, ns = bc.train_render("grad_static", precision, **extra)[:3]
     return ({k: v.detach() for k, v in ret.items() if v is not None},
             {k: p.grad for k, p in ns.named_parameters() if p.grad is not None and k.endswith("weight")})
 
@@ -269,7 +232,6 @@ def test_switch_default_unknown_and_precision_16(hip, monkeypatch):
     _render_static(32)
     assert spy.seen and set(spy.seen) == {zh.GEMM_LIBRARY}
     # ... and in a module's own forward under autograd, which has no args and reads the environment alone
-    from test_hip_ops import _mlp_module
     _, inp, _, _ = _mlp_setup("mlp_static_mvs20")
     net, x = _mlp_module(inp), G(inp["x"])[0].requires_grad_(True)
     del spy.seen[:]

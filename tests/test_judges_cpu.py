@@ -1,41 +1,37 @@
-"""CPU: the comparison helpers of the GPU tests, judged themselves.  A kernel that writes a NaN or an infinity into part of
-its output must turn its test red: `err > tol` is false for a NaN error, so every helper decides with `~(err <= tol)` or
-asserts finiteness first, and this file holds each of them to it.
+"""CPU: the comparison rules of the suite (tests/judges.py, and the family judges of the *_cases modules), judged
+themselves.  A kernel that writes a NaN or an infinity into part of its output must turn its test red: `err > tol` is
+false for a NaN error, so every rule decides with `~(err <= tol)` or asserts finiteness first, and this file holds each of
+them to it, as each family of call sites calls it.
 
-Every helper is wrapped as run(got, want) on float64 arrays with a function tol(want, index) restating its bound at one
+Every rule is wrapped as run(got, want) on float64 arrays with a function tol(want, index) restating its bound at one
 element.  For each: identical input passes; an error of 0.9 tol passes and one of 1.1 tol fails (the bound is the one the
-helper documents, not a wider one); one NaN or one +inf in `got` fails; a NaN in `want` against a finite `got` fails.
-Importing the GPU test modules touches no GPU."""
+rule documents, not a wider one); one NaN or one +inf in `got` fails; a NaN in `want` against a finite `got` fails.
+Last, the structure that keeps this file short: no module of tests/ imports a test module."""
+import ast
+import glob
+import os
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+import backward_cases as bc
 import disc_cases as dc
 import grad_edge_cases as ge
+import judges
+import optim_amp_cases as ac
 import optim_cases as oc
 import train_gemm_cases as tg
-import test_hip_backward
-import test_hip_costreg_paths
-import test_hip_disc
-import test_hip_fold
-import test_hip_fullsize
-import test_hip_image_metrics
-import test_hip_lpips
-import test_hip_ops
-import test_hip_optim_amp
-import test_hip_precision
-import test_hip_train_gemm
-import test_hip_volume
+from judges import ATOL, RTOL
 
-ATOL, RTOL = test_hip_ops.ATOL, test_hip_ops.RTOL
 WANT = np.linspace(0.5, 2.0, 12).reshape(4, 3)             # four "rays"; the largest entry is the last one
 AT = (1, 2)                                                # the element the tests disturb (not the largest)
 
 
 class Judge:
-    """run(got, want) raises AssertionError or returns; tol(want, index) is the helper's bound at that element."""
+    """run(got, want) raises AssertionError or returns; tol(want, index) is the rule's bound at that element.  The name is
+    the call-site family's: the test module and what it calls (or called, before the rule moved to judges.py)."""
 
     def __init__(self, name, run, tol, want=WANT, at=AT):
         self.name, self.run, self.tol, self.want, self.at = name, run, tol, np.array(want, np.float64), at
@@ -51,7 +47,7 @@ def _scaled(want, at):
 
 def _check_elements(got, want):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).reshape(1, 2, 2, 3)   # noqa: E731
-    test_hip_costreg_paths.check_elements("judge", t(got), t(want), torch.ones(1, 2, 2, 3, dtype=torch.float64), 1e-3, rows_per_tile=2)
+    judges.check_elements("judge", t(got), t(want), torch.ones(1, 2, 2, 3, dtype=torch.float64), 1e-3, rows_per_tile=2)
 
 
 # -------------------------------------------------------------------------- Adam: the reference is computed, not given
@@ -73,7 +69,7 @@ def _adam(got, want, where=None):
 
 def _adam_amp(got, want, absent=()):
     world = SimpleNamespace(ns=[5, 7], tensor_of=np.repeat([0, 1], [5, 7]))
-    test_hip_optim_amp._judge(world, [_ADAM_T, _ADAM_T], _adam_old(want), (got, _ADAM_M, _ADAM_V), _ADAM_G, [oc.LR, oc.LR], 1.0,
+    ac.judge(world, [_ADAM_T, _ADAM_T], _adam_old(want), (got, _ADAM_M, _ADAM_V), _ADAM_G, [oc.LR, oc.LR], 1.0,
                               absent=absent, label="judge")
 
 
@@ -95,7 +91,7 @@ def _disc_compare(key):
             g[key], w[key] = got, want
         else:
             g[key], w[key] = float(got[0]), float(want[0])
-        test_hip_disc._compare(g, w, 32, 16, "judge")
+        dc.compare(g, w, 32, 16, "judge")
     return run
 
 
@@ -111,43 +107,57 @@ def _gemm(got, want, lib=None):
     """`want` is the float64 product of the operands: check_bound computes it itself, so a disturbed `want` is refused
     here as a disturbed reference."""
     assert np.array_equal(want, _GEMM_REF, equal_nan=False), "the reference is not the operands' product"
-    test_hip_train_gemm.check_bound(_ZH, tg.OP_NT, _GEMM_A, _GEMM_B, {0: _GEMM_LIB if lib is None else lib, 1: got}, name="judge")
+    tg.check_bound(_ZH, tg.OP_NT, _GEMM_A, _GEMM_B, {0: _GEMM_LIB if lib is None else lib, 1: got}, name="judge")
 
 
 def _gemm_tol(want, at):
     return tg.bound_factor(tg.ratio(_GEMM_LIB, _GEMM_REF, _GEMM_MAG)) * _GEMM_MAG[at]
 
 
+def _scaled_at(atol, rtol, floor=0.0):
+    return lambda w, at: atol * (np.abs(w).max() + floor) + rtol * abs(w[at])
+
+
+def _ratio_below(ratio, bound, **kw):
+    """The call sites' `assert ratio(got, want) < bound`: a NaN ratio fails it."""
+    def run(got, want):
+        r = ratio(torch.from_numpy(got), torch.from_numpy(want), **kw)
+        assert r < bound, r
+    return run
+
+
 JUDGES = [
-    Judge("ops.close", lambda g, w: test_hip_ops.close(g, w, name="judge"), _elementwise),
-    Judge("ops.close/tensor", lambda g, w: test_hip_ops.close(torch.from_numpy(g), w, name="judge"), _elementwise),
-    Judge("backward.gclose", lambda g, w: test_hip_backward.gclose(g, w, "judge"), _scaled),
-    Judge("precision.close_rays", lambda g, w: test_hip_precision.close_rays(torch.from_numpy(g), w, ATOL, RTOL, "judge"), _elementwise),
-    Judge("fullsize.close_most", lambda g, w: test_hip_fullsize.close_most(torch.from_numpy(g), torch.from_numpy(w), 2e-3, "judge", 0.0),
+    Judge("ops.close", lambda g, w: judges.close(g, w, name="judge"), _elementwise),
+    Judge("ops.close/tensor", lambda g, w: judges.close(torch.from_numpy(g), w, name="judge"), _elementwise),
+    Judge("backward.gclose", lambda g, w: bc.gclose(g, w, "judge"), _scaled),
+    Judge("precision.close_rays", lambda g, w: judges.close_rays(torch.from_numpy(g), w, ATOL, RTOL, "judge"), _elementwise),
+    Judge("fullsize.close_most", lambda g, w: judges.close_rays(torch.from_numpy(g), torch.from_numpy(w), 2e-3, 0, "judge", max_share=0.0),
           lambda w, at: 2e-3),
-    Judge("fold.elements_close", test_hip_fold.elements_close, _elementwise),
+    Judge("fold.elements_close", lambda g, w: judges.finite_close(g, w, "judge", ATOL, RTOL), _elementwise),
+    Judge("image_metrics._close", lambda g, w: judges.finite_close(g, w, "judge", ATOL, RTOL, show=True), _elementwise),
+    Judge("disc_cpu._close", lambda g, w: judges.finite_close(g, w, "judge", 2e-6, 2e-5), lambda w, at: 2e-6 + 2e-5 * abs(w[at])),
     Judge("costreg_paths.check_elements", _check_elements, lambda w, at: 1e-3 + 2.0 ** -23 * abs(w[at])),
     Judge("optim_cases.judge", _adam, _adam_tol, want=_ADAM_P, at=(4,)),
     Judge("optim_cases.judge/where", lambda g, w: _adam(g, w, where=np.arange(_ADAM_N) != 0), _adam_tol, want=_ADAM_P, at=(4,)),
     Judge("optim_amp._judge", _adam_amp, _adam_tol, want=_ADAM_P, at=(4,)),
-    Judge("image_metrics._close", lambda g, w: test_hip_image_metrics._close(g, w, "judge"), _elementwise),
-    Judge("lpips._layers_close", lambda g, w: test_hip_lpips._layers_close(g, w, "judge"), lambda w, at: RTOL * w[at]),
-    Judge("lpips._grad_close", lambda g, w: test_hip_lpips._grad_close(g, w, "judge"),
-          lambda w, at: ATOL * np.abs(w).max() + RTOL * abs(w[at])),
-    Judge("lpips._l2_close", lambda g, w: test_hip_lpips._l2_close(g, w, "judge"), lambda w, at: RTOL * np.linalg.norm(w)),
-    Judge("disc._close_grad", lambda g, w: test_hip_disc._close_grad(g, w, "judge"),
-          lambda w, at: ATOL * np.abs(w).max() + RTOL * abs(w[at])),
-    Judge("disc._close_l2", lambda g, w: test_hip_disc._close_l2(g, w, "judge"), lambda w, at: RTOL * np.linalg.norm(w)),
+    Judge("lpips._layers_close", lambda g, w: judges.relative_close(g, w, "judge", RTOL), lambda w, at: RTOL * w[at]),
+    Judge("lpips._grad_close", lambda g, w: judges.scaled_close(g, w, "judge", ATOL, RTOL, nonzero=True), _scaled_at(ATOL, RTOL)),
+    Judge("disc._close_grad", lambda g, w: judges.scaled_close(g, w, "judge", ATOL, RTOL, nonzero=True), _scaled_at(ATOL, RTOL)),
+    Judge("sf_patch.grad_walks", lambda g, w: judges.scaled_close(g, w, "judge", ATOL, RTOL), _scaled_at(ATOL, RTOL)),
+    Judge("lpips._l2_close", lambda g, w: judges.l2_close(g, w, "judge", RTOL), lambda w, at: RTOL * np.linalg.norm(w)),
+    Judge("disc._close_l2", lambda g, w: judges.l2_close(g, w, "judge", RTOL), lambda w, at: RTOL * np.linalg.norm(w)),
     Judge("disc._compare/norm", _disc_compare("disc__grad_norm__0"), lambda w, at: RTOL * w[at], want=[_DISC_NORM], at=(0,)),
     Judge("disc._compare/dots", _disc_compare("disc__grad_dots__0"), lambda w, at: RTOL * _DISC_NORM * _DISC_DNORM[at[0]],
           want=[0.5, -1.0, 2.0, 0.25], at=(1,)),
     Judge("disc._compare/scalar", _disc_compare("disc__total"), _elementwise, want=[1.5], at=(0,)),
-    Judge("volume.all_but_few_close", lambda g, w: test_hip_volume.all_but_few_close(g, w, "judge"),
-          lambda w, at: 1e-4 * np.abs(w).max() + 1e-3 * abs(w[at])),
+    Judge("volume.all_but_few_close", lambda g, w: judges.all_but_few_close(g, w, "judge", max_share=2e-3), _scaled_at(1e-4, 1e-3)),
     Judge("train_gemm.check_bound", _gemm, _gemm_tol, want=_GEMM_REF),
     Judge("grad_edge_cases.rows_close", lambda g, w: ge.rows_close(g, w, 1, "judge"),
           lambda w, at: ge.REL * np.abs(w[at[0]]).max() + ge.REL * abs(w[at])),
     Judge("grad_edge_cases.tensor_close", lambda g, w: ge.tensor_close(g, w, "judge"), _scaled),
+    Judge("costreg._rel", _ratio_below(judges.max_ratio, 2e-4), lambda w, at: 2e-4 * np.abs(w).max()),
+    Judge("builder_nets_golden._rel", _ratio_below(judges.max_ratio, 2e-5, floor=0), lambda w, at: 2e-5 * np.abs(w).max()),
+    Judge("train16.rel", _ratio_below(judges.l2_ratio, 2e-3), lambda w, at: 2e-3 * np.linalg.norm(w)),
 ]
 IDS = [j.name for j in JUDGES]
 
@@ -190,28 +200,28 @@ def test_non_finite_want_against_a_finite_got_fails(j, value):
 # -------------------------------------------------------------------------- close: its one allowance
 def test_close_takes_nan_for_nan_at_the_same_index_only():
     a = _with(WANT, AT, np.nan)
-    test_hip_ops.close(a, a.copy(), name="same")
-    test_hip_ops.close(torch.from_numpy(a).float(), a.copy(), name="same, from a float32 tensor")
+    judges.close(a, a.copy(), name="same")
+    judges.close(torch.from_numpy(a).float(), a.copy(), name="same, from a float32 tensor")
     with pytest.raises(AssertionError):
-        test_hip_ops.close(a, _with(WANT, (2, 0), np.nan), name="elsewhere")
+        judges.close(a, _with(WANT, (2, 0), np.nan), name="elsewhere")
     with pytest.raises(AssertionError):                            # both hold one NaN each AND share one: the odd one counts
-        test_hip_ops.close(_with(a, (2, 0), np.nan), a, name="one more")
+        judges.close(_with(a, (2, 0), np.nan), a, name="one more")
 
 
 def test_close_takes_an_infinity_only_for_the_same_infinity():
     a = _with(WANT, AT, np.inf)
-    test_hip_ops.close(a, a.copy(), name="same")
+    judges.close(a, a.copy(), name="same")
     for got, want in ((a, _with(WANT, AT, -np.inf)), (a, WANT), (WANT, a), (a, _with(WANT, AT, np.nan)), (_with(WANT, AT, np.nan), a),
                       (_with(WANT, AT, 1e308), a)):
         with pytest.raises(AssertionError):
-            test_hip_ops.close(got, want, name="differs")
+            judges.close(got, want, name="differs")
     with pytest.raises(AssertionError):                            # rtol |want| must not turn infinite
-        test_hip_ops.close(WANT, a, rtol=1.0, name="finite against inf")
+        judges.close(WANT, a, rtol=1.0, name="finite against inf")
 
 
 def test_close_refuses_another_shape():
     with pytest.raises(AssertionError):
-        test_hip_ops.close(WANT[:, :1], WANT, name="broadcast")
+        judges.close(WANT[:, :1], WANT, name="broadcast")
 
 
 # -------------------------------------------------------------------------- the share-of-rays helpers
@@ -222,7 +232,7 @@ def _rays(n):
 def test_close_rays_never_counts_a_non_finite_ray_against_its_allowance():
     w = _rays(4)
     off = _with(w, AT, w[AT] + 1.0)
-    rays = lambda g, w, k: test_hip_precision.close_rays(torch.from_numpy(g), w, ATOL, RTOL, "judge", max_bad=k)   # noqa: E731
+    rays = lambda g, w, k: judges.close_rays(torch.from_numpy(g), w, ATOL, RTOL, "judge", max_bad=k)   # noqa: E731
     rays(off, w, 1)                                                # one ray flipped between two finite values: excused
     with pytest.raises(AssertionError):
         rays(off, w, 0)
@@ -239,9 +249,10 @@ def test_close_rays_never_counts_a_non_finite_ray_against_its_allowance():
 
 
 def test_close_most_never_counts_a_non_finite_ray_against_its_allowance():
+    """close_rays with a share of the rays for its allowance (test_hip_fullsize.py)."""
     w = _rays(200)
     off = _with(w, AT, w[AT] + 1.0)
-    most = lambda g, w: test_hip_fullsize.close_most(torch.from_numpy(g), torch.from_numpy(w), 2e-3, "judge")      # noqa: E731
+    most = lambda g, w: judges.close_rays(torch.from_numpy(g), torch.from_numpy(w), 2e-3, 0, "judge", max_share=0.005)      # noqa: E731
     most(off, w)                                                   # 1 ray of 200 = the default 0.5 %
     with pytest.raises(AssertionError):
         most(_with(off, (3, 0), off[3, 0] + 1.0), w)               # 2 of 200
@@ -255,7 +266,7 @@ def test_close_most_never_counts_a_non_finite_ray_against_its_allowance():
 
 def test_volume_rule_never_excuses_a_non_finite_entry():
     w = np.linspace(0.5, 2.0, 3000).reshape(1000, 3)
-    few = lambda g, w: test_hip_volume.all_but_few_close(g, w, "judge")                                              # noqa: E731
+    few = lambda g, w: judges.all_but_few_close(g, w, "judge", max_share=2e-3)                                       # noqa: E731
     few(_with(w, AT, w[AT] + 1.0), w)                              # 1 of 3000 entries on another tap: under 0.2 %
     with pytest.raises(AssertionError):
         few(np.where(np.arange(3000).reshape(1000, 3) % 400 == 0, w + 1.0, w), w)      # 8 of 3000
@@ -293,3 +304,36 @@ def test_a_non_finite_library_result_does_not_set_the_gemm_bound(value):
         _gemm(_GEMM_REF + 10.0, _GEMM_REF, lib=lib)
     with pytest.raises(AssertionError):
         _gemm(_GEMM_REF.copy(), _GEMM_REF, lib=lib)
+
+
+# -------------------------------------------------------------------------- the options of the scaled rule
+def test_scaled_rule_options():
+    """nonzero refuses an all-zero reference, which without it (and without a floor) admits only an exact copy;
+    exact_zeros holds the entries of a zero reference to exactly zero inside an otherwise passing tensor."""
+    zero = np.zeros((4, 3))
+    judges.scaled_close(zero, zero, "judge", ATOL, RTOL)
+    bc.gclose(zero, zero, "judge")
+    for run in (lambda: judges.scaled_close(zero, zero, "judge", ATOL, RTOL, nonzero=True),
+                lambda: judges.scaled_close(zero + 1e-30, zero, "judge", ATOL, RTOL),
+                lambda: judges.scaled_close(WANT[:, :1], WANT, "judge", ATOL, RTOL)):
+        with pytest.raises(AssertionError):
+            run()
+    w = _with(WANT, AT, 0.0)
+    assert ge.tensor_close(_with(w, AT, 1e-6), w, "judge") == pytest.approx(1e-6 / 2.0)
+    with pytest.raises(AssertionError):
+        ge.tensor_close(_with(w, AT, 1e-6), w, "judge", exact_zeros=True)
+
+
+# -------------------------------------------------------------------------- the structure
+def test_no_module_of_the_suite_imports_a_test_module():
+    """What tests share lives in judges.py, gpu_cases.py and the *_cases modules: a test module that is imported runs its
+    module-level statements inside every test that reaches it, and drags the GPU tests' helpers into the CPU ones."""
+    found = []
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "*.py"))):
+        with open(path) as f:
+            tree = ast.parse(f.read(), path)
+        for node in ast.walk(tree):
+            names = [a.name for a in node.names] if isinstance(node, ast.Import) else \
+                [node.module or ""] if isinstance(node, ast.ImportFrom) else []
+            found += ["%s:%d imports %s" % (os.path.basename(path), node.lineno, n) for n in names if n.split(".")[0].startswith("test_")]
+    assert not found, found

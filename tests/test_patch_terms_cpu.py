@@ -11,13 +11,13 @@ import pytest
 import torch
 
 import patch_cases as pc
-from test_dropin_overlay import caller_dir, clean_modules  # noqa: F401  (the stand-in caller modules)
+from judges import ATOL, RTOL
+from package_cases import caller_dir, clean_modules  # noqa: F401  (the stand-in caller modules)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # test_oracle_golden's two bounds: scalar values within its value bound, gradients within its gradient bound (1e-4 of
 # the array's scale + 1e-3 relative)
 VALUE_ATOL, VALUE_RTOL = 2e-6, 2e-5
-ATOL, RTOL = 1e-4, 1e-3
 
 
 def _value(got, want, name):

@@ -13,9 +13,9 @@ import pytest
 import torch
 
 import sf_loss_cases as sc
-from test_dropin_overlay import PKG, caller_dir, clean_modules  # noqa: F401  (the stand-in caller modules)
+from judges import ATOL, RTOL
+from package_cases import PKG, caller_dir, clean_modules  # noqa: F401  (the stand-in caller modules)
 
-ATOL, RTOL = 1e-4, 1e-3                                   # test_hip_ops.ATOL / RTOL: the bounds the GPU tests use
 BOUNDARY = ((3, 193), (2, 68), (2, 69), (4, 3))           # the GPU tests' boundary shapes, at sc.SEED
 
 

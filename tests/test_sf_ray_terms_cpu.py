@@ -75,15 +75,14 @@ def test_wrapper_refuses_bad_arguments_before_touching_the_library(monkeypatch):
         zest_hip.sf_ray_bwd(flat, None, 0)
     # the whole step: an unknown ray_terms value is refused before anything else; both known values refuse a CPU batch
     # and an empty one with the library untouched
-    from test_sf_step_cpu import _cpu_results
     hp, cams = types.SimpleNamespace(**ss.SHIPPED), torch.eye(4).repeat(1, 2, 1, 1)
     with pytest.raises(RuntimeError, match="ray_terms must be"):
-        L.train_sf_step_loss(_cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms="triton")
+        L.train_sf_step_loss(ss.cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms="triton")
     for way in ("hip", "torch"):
         with pytest.raises(RuntimeError, match="runs only on a HIP device"):
-            L.train_sf_step_loss(_cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms=way)
+            L.train_sf_step_loss(ss.cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms=way)
         with pytest.raises(RuntimeError, match="empty batch"):
-            L.train_sf_step_loss(_cpu_results(R=0), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms=way)
+            L.train_sf_step_loss(ss.cpu_results(R=0), (1, 3, 3, ss.H, ss.W), ss.FOCAL, cams, 5, 12, hp, 0, 30, ray_terms=way)
 
 
 @pytest.mark.parametrize("R", rc.SIZES)

@@ -9,8 +9,8 @@ import pytest
 import torch
 
 import sf_step_cases as ss
+from judges import ATOL, RTOL
 
-ATOL, RTOL = 1e-4, 1e-3                                   # test_hip_ops.ATOL / RTOL: the bounds the GPU tests use
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -77,17 +77,6 @@ def test_configurations_take_the_reference_branches():
     assert a["global_step"] // (ss.DECAY_ITERATION * 1000) == 0 and b["global_step"] // (ss.DECAY_ITERATION * 1000) == 2
 
 
-def _cpu_results(R=4, S=10):
-    r = {k: torch.zeros(1, R, S, 3) for k in ss.SF + ss.PTS}
-    r.update({k: torch.zeros(1, R, S) for k in ss.PROB + ("weights_ref_dy", "raw_blend_w")})
-    r.update({k: torch.zeros(1, R, 3) for k in ss.RGB + ("target_s",)})
-    r.update({k: torch.zeros(1, R, 2) for k in ("rays_flow_fwd_gt", "rays_flow_bwd_gt")})
-    r.update({k: torch.zeros(1, R) for k in ("prob_map_post", "prob_map_prev", "weights_map_dd", "rays_mask_fwd_gt",
-                                             "rays_mask_bwd_gt", "depth_map_ref_dy", "depth_gt")})
-    r["chain_bwd"], r["chain_5frames"] = True, True
-    return r
-
-
 def test_wrappers_refuse_bad_arguments_before_touching_the_library(monkeypatch):
     import zest_hip
     import zest_losses as L
@@ -123,8 +112,8 @@ def test_wrappers_refuse_bad_arguments_before_touching_the_library(monkeypatch):
     # the whole step: refused at its first per-sample call, before any launch
     hp = types.SimpleNamespace(**ss.SHIPPED)
     with pytest.raises(RuntimeError, match="runs only on a HIP device"):
-        L.train_sf_step_loss(_cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, torch.eye(4).repeat(1, 2, 1, 1), 5, 12, hp, 0, 30)
-    empty = _cpu_results(R=0)
+        L.train_sf_step_loss(ss.cpu_results(), (1, 3, 3, ss.H, ss.W), ss.FOCAL, torch.eye(4).repeat(1, 2, 1, 1), 5, 12, hp, 0, 30)
+    empty = ss.cpu_results(R=0)
     with pytest.raises(RuntimeError, match="empty batch"):
         L.train_sf_step_loss(empty, (1, 3, 3, ss.H, ss.W), ss.FOCAL, torch.eye(4).repeat(1, 2, 1, 1), 5, 12, ss.SHIPPED, 0, 30)
 

@@ -17,7 +17,6 @@ import pytest
 import engine_format_cases as ef
 import train16_cases as tc
 import train16_format_cases as tf
-from test_hip_train16 import oracle_grads
 
 
 def _same(a, b):
@@ -56,7 +55,7 @@ def test_unrounded_restatement_is_the_gradient(case):
     x, gw = tf._draw(case, 40, 5)
     out, fwd, _ = tf.forward_values(inp["state"], spec, x, rounding=False)
     gx, gp = tf.restate_backward(inp["state"], desc, x, out, gw, fwd, rounding=False)
-    y, gx_ref, gp_ref = oracle_grads(inp, x, gw, bf16_operands=False)
+    y, gx_ref, gp_ref = tc.oracle_grads(inp, x, gw, bf16_operands=False)
     assert np.abs(out - y).max() == 0
     assert np.abs(gx - gx_ref[:, :gx.shape[1]]).max() <= 1e-10 * np.abs(gx_ref).max()
     keys = tc.grad_keys(inp)
@@ -130,7 +129,7 @@ def test_gpu_case_meets_the_conditions_and_its_judges_reject_every_fault(case, M
     print("train16 format %s: restatements flip %s of the rows at a = %g; worst tile of a restatement %.2e of its tensor's "
           "rms tile" % (name, ", ".join("%s %.2f %% (cap %.2f %%)" % (g, 100 * s, 100 * c) for g, (s, c) in shares.items()),
                         tf.ROW_ATOL, spread))
-    oracle = oracle_grads(inp, x, gw)
+    oracle = tc.oracle_grads(inp, x, gw)
     assert _legacy_passes(inp, desc, M, gx, gp, oracle), "%s: the restatement itself is outside today's bounds" % name
     for fault in tf.faults_of(inp):
         fx, fp = tf.restate_backward(inp["state"], desc, x, out, gw, fwd, acc="f32", fault=fault)

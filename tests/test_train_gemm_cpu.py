@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import train_gemm_cases as tg
-from test_capi_symbols import _declared
+from package_cases import _declared
 
 NEW_NAMES = ["zest_mlp_train_bwd_ex", "zest_mlp_train_fwd_ex", "zest_mlp_train_workspace_floats_ex", "zest_train_gemm",
              "zest_train_gemm_chunk_rows", "zest_train_gemm_workspace_floats"]

@@ -156,3 +156,21 @@ def isolation(K):
     v = np.float32(1.0 + 2.0 ** -9 + 2.0 ** -18)
     s = np.where(np.arange(K) % 2 == 0, 1.0, -1.0).astype(np.float32)
     return (s * v)[None, :], (s * v)[None, :]
+
+
+def check_bound(zh, op, a, b, got, c0=None, name=""):
+    """|got - ref64| <= c sum |a||b| per entry, c = max(4 r_lib, 2^-21) with r_lib measured here.  With beta = 1 the
+    old value of c is one more term of the sum (c0 . 1), in the reference and in the magnitude."""
+    A, B = as_ik_jk(op, a, b)
+    ref, mag = ref64(A, B)
+    if c0 is not None:
+        ref, mag = ref + c0, mag + np.abs(c0)
+    assert np.all(np.isfinite(ref)) and np.all(np.isfinite(mag)), name
+    # the library's error sets the bound: a non-finite library result would make it infinite, or NaN
+    assert np.all(np.isfinite(got[zh.GEMM_LIBRARY])), "%s: the library result is not finite" % name
+    assert np.all(np.isfinite(got[zh.GEMM_SPLIT_BF16])), name
+    r_lib, r_split = ratio(got[zh.GEMM_LIBRARY], ref, mag), ratio(got[zh.GEMM_SPLIT_BF16], ref, mag)
+    c = bound_factor(r_lib)
+    print("%s: library %.3g  split %.3g  bound %.3g" % (name, r_lib, r_split, c))
+    assert np.isfinite(c), "%s: bound %r from the library's %r" % (name, c, r_lib)
+    assert r_split <= c, "%s: split %.3g > bound %.3g (library %.3g)" % (name, r_split, c, r_lib)

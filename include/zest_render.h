@@ -256,6 +256,34 @@ int zest_volume_cost_bwd(const float *feats_cl, const float *proj, const float *
 int zest_homo_warp_bwd(const float *proj, const float *depth, const float *grid_in, int C, int D, int H,
                        int W, int Hp, int Wp, int pad, const float *g_warped, float *g_src, void *stream);
 
+/* ---- order-independent gradients (opt-in: args.zest_deterministic / ZEST_DETERMINISTIC=1) ----
+ * The scatter-adds above and zest_encode_bwd's volume gradient add floats with atomics: the bits of the result depend
+ * on the order in which workgroups arrive.  The *_det forms compute every contribution with the same fp32 expression
+ * and add it in 64-bit fixed point (csrc/fixed_accum.cuh) at a scale chosen on the device from the largest |gradient| of
+ * the call (the sweep: and the largest |feature|) and its number of contributions: the result is the same for every
+ * order of arrival, so permuting the rays / planes of the input gives the same bits.  Differences to the default forms:
+ *   - the fp32 result is WRITTEN in full (no zeroing beforehand, nothing is added to what it held);
+ *   - `work`: *_det_work_bytes(...) bytes, 16-byte aligned, zeroed by the call itself (a 64-byte header and one 64-bit
+ *     accumulator per element of the result); no state is kept between calls and none in the library;
+ *   - each value is rounded to a multiple of q <= 2^-30 max|contribution|; max|g| = 0 gives zeros;
+ *   - a NaN or an infinity in the gradient (the sweep: or the features), or a contribution that overflows, makes the
+ *     WHOLE result NaN - the default forms poison only the elements they touch;
+ *   - more than 2^32 contributions per call (R S 8; voxels x V x 4; voxels x 4) are refused.
+ * Launches only (a memset node, a pre-pass, the scatter kernel, a finishing kernel): nothing is read back to the host.
+ * zest_encode_bwd_det needs vol_cl and g_vol_cl (without a volume gradient zest_encode_bwd adds nothing up). */
+size_t zest_encode_bwd_det_work_bytes(int D, int Hv, int Wv);
+int zest_encode_bwd_det(const float *g_x, const float *ndc, int R, int S, int has_time, float t,
+                        const float *vol_cl, int D, int Hv, int Wv, int V, float *g_ndc, float *g_vol_cl,
+                        void *work, void *stream);
+size_t zest_volume_cost_bwd_det_work_bytes(int V, int H, int W);
+int zest_volume_cost_bwd_det(const float *feats_cl, const float *proj, const float *depth, int V, int C,
+                             int D, int H, int W, int pad, const float *g_img_feat, float *g_feats_cl,
+                             void *work, void *stream);
+size_t zest_homo_warp_bwd_det_work_bytes(int C, int H, int W);
+int zest_homo_warp_bwd_det(const float *proj, const float *depth, const float *grid_in, int C, int D, int H,
+                           int W, int Hp, int Wp, int pad, const float *g_warped, float *g_src, void *work,
+                           void *stream);
+
 /* ---- loss-side reductions over the samples of a ray -------------------
  * zest_distortion_fwd: distortion_loss (reference losses.py:53-87) per ray.  weights [R,S];
  *   t_vals [t_rows,S] with t_rows 1 or R.  loss_ray [R] (the reference returns their sum);
@@ -722,7 +750,7 @@ int zest_volume_from_cl(const float *vol_cl, int D, int H, int W, float *vol, vo
  *                         (capturable in a HIP graph by construction; not covered by a test).  With it the
  *                         weight and data gradients are bit-reproducible from run to run (fixed summation order,
  *                         no atomics); the BIAS gradients still are not: their column sums use float atomics in
- *                         either mode.  Non-finite inputs give non-finite outputs (inf - inf in the split), not
+ *                         either mode, unless the backward is zest_mlp_train_bwd_det (below).  Non-finite inputs give non-finite outputs (inf - inf in the split), not
  *                         necessarily the library's kind of non-finite.
  * The workspace of the _ex calls is zest_mlp_train_workspace_floats_ex floats (never less than the plain query). */
 enum { ZEST_GEMM_LIBRARY = 0, ZEST_GEMM_SPLIT_BF16 = 1 };
@@ -740,6 +768,17 @@ int zest_mlp_train_fwd_ex(const zest_mlp_desc *desc, const float *const *params,
 int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
                           const float *saved, const float *out, const float *g_out, float *workspace,
                           float *g_x, float *const *g_params, void *stream, int gemm);
+/* zest_mlp_train_bwd_ex with the bias gradients through per-block partials added in block order instead of float
+ * atomics: with ZEST_GEMM_SPLIT_BF16 every gradient of the call then has the same bits on every call.  workspace:
+ * zest_mlp_train_workspace_floats_det floats (the _ex size and room for the partials). */
+size_t zest_mlp_train_workspace_floats_det(const zest_mlp_desc *desc, int M, int gemm);
+/* The ordered column sums of that backward on their own: out[n] = sum_m a[m lda + n], n < N <= 256, as per-block partials
+ * (256 rows each, into `work`: zest_colsum_ordered_work_floats floats) added in block order by a second launch. */
+size_t zest_colsum_ordered_work_floats(int M, int N);
+int zest_colsum_ordered(const float *a, int M, int N, int lda, float *work, float *out, void *stream);
+int zest_mlp_train_bwd_det(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
+                           const float *saved, const float *out, const float *g_out, float *workspace,
+                           float *g_x, float *const *g_params, void *stream, int gemm);
 
 /* One GEMM of that path, fp32 row-major operands with leading dimensions, through either kind (`gemm`):
  *   ZEST_GEMM_OP_NT  c[M,N] (ldc) = a[M,K] (lda) . b[N,K]^T (ldb) + beta c       (a = X, b = Wt, c = Y)

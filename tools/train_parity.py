@@ -5,6 +5,7 @@
   oracle   the CPU oracle (reference op sequence, oracle/zest_oracle.py) under torch autograd, fp32
   hip32    renderer.rendering(..., val=False) under autograd, --precision 32 (HIP kernels + rocBLAS sgemm; with ZEST_TRAIN_GEMM=split
            in the environment the GEMMs run on the three-term bf16 MFMA kernels instead)
+  hip32split  hip32 with args.zest_train_gemm = "split", whatever the environment says
   hip16    the same call with --precision 16: both MLPs forward and backward on the bf16 MFMA kernels
 
 on a loss shaped like the reference's training step (train.py:346-585: colour terms on the blended, the static and
@@ -16,7 +17,13 @@ gradient component by its running magnitude, so two fp32 implementations that di
 after a few dozen steps, and that spread - not 0.05 dB - is what a 200-step delta on a 96-ray scene can resolve -
 and how long hip32 follows the oracle step by step.
 
-    python tools/train_parity.py [--steps 200] [--rays 96] [--samples 24] [--modes oracle,hip32,hip16]
+--deterministic sets args.zest_deterministic (order-independent gradients: zest_networks.deterministic_choice) in the hip
+modes; --repeat N trains every hip mode N times from the same state and reports whether the loss curves are identical
+to the last bit ("repeats_identical"): with the switch on they are wherever every kernel of the step is the project's
+own; behind the default zest_train_gemm = "library" the GEMMs are rocBLAS's, and what they do is a finding.
+
+    python tools/train_parity.py [--steps 200] [--rays 96] [--samples 24] [--modes oracle,hip32,hip32split,hip16]
+                                 [--deterministic] [--repeat 2]
 """
 import argparse
 import json
@@ -93,7 +100,10 @@ def train_oracle(sc, tgt, tgt_s, steps, R):
     return losses, psnr(held["rgb_map_ref"], tgt[R:]), psnr(held["rgb_map"], tgt_s[R:]), psnr(fit["rgb_map_ref"], tgt[:R])
 
 
-def train_hip(sc, tgt, tgt_s, steps, R, precision):
+HIP_MODES = {"hip32": (32, None), "hip32split": (32, "split"), "hip16": (16, None)}      # mode -> (precision, zest_train_gemm)
+
+
+def train_hip(sc, tgt, tgt_s, steps, R, precision, gemm=None, deterministic=False):
     import zest_networks as networks
     import zest_renderer as renderer
     from test_hip_render import build_nets
@@ -101,7 +111,8 @@ def train_hip(sc, tgt, tgt_s, steps, R, precision):
     ns, nd = build_nets(sc)
     opt = torch.optim.Adam(list(ns.parameters()) + list(nd.parameters()), lr=LR)
     args = SimpleNamespace(netchunk=4096, feat_dim=sc["feat_dim"], feat_dim_dy=24, img_downscale=1.0,
-                           use_color_volume=False, net_type="v0", precision=precision)
+                           use_color_volume=False, net_type="v0", precision=precision, zest_train_gemm=gemm,
+                           zest_deterministic=deterministic)
     cam = {"w2cs": G(sc["w2cs"]), "intrinsics": G(sc["intrinsics"])}
     nb_cam = {"w2cs": G(sc["nb_w2cs"]), "intrinsics": G(sc["nb_intrinsics"])}
     rays = {k: G(sc[k]) for k in ("rays_pts", "rays_ndc", "depth_candidates", "rays_dir")}
@@ -130,16 +141,24 @@ def train_hip(sc, tgt, tgt_s, steps, R, precision):
             psnr(fit["rgb_map_ref"][0].cpu(), tgt[:R].cpu()))
 
 
-def run(steps=200, rays=96, samples=24, seed=901, modes=("oracle", "hip32", "hip16")):
+def run(steps=200, rays=96, samples=24, seed=901, modes=("oracle", "hip32", "hip16"), deterministic=False, repeat=1):
     sc, tgt, tgt_s = scene(seed, rays, samples)
-    out = {"steps": steps, "rays": rays, "samples": samples, "lr": LR, "held_out_rays": HELD_OUT}
+    out = {"steps": steps, "rays": rays, "samples": samples, "lr": LR, "held_out_rays": HELD_OUT,
+           "deterministic": bool(deterministic), "repeat": repeat}
     for m in modes:
+        same = None
         if m == "oracle":
             torch.set_num_threads(min(8, os.cpu_count() or 1))
             r = train_oracle(sc, tgt, tgt_s, steps, rays)
         else:
-            r = train_hip(sc, tgt, tgt_s, steps, rays, 32 if m == "hip32" else 16)
+            runs = [train_hip(sc, tgt, tgt_s, steps, rays, *HIP_MODES[m], deterministic=deterministic) for _ in range(repeat)]
+            r = runs[0]
+            if repeat > 1:      # Python floats of the fp32 losses: equal only if every step gave the same bits
+                same = {"repeats_identical": all(x[0] == r[0] for x in runs[1:]),
+                        "first_step_that_differs": min((next((i for i, (p, q) in enumerate(zip(x[0], r[0])) if p != q), steps)
+                                                        for x in runs[1:]))}
         out[m] = {"loss": r[0], "psnr_blend_db": r[1], "psnr_static_db": r[2], "psnr_train_rays_db": r[3]}
+        out[m].update(same or {})
     return out
 
 
@@ -159,14 +178,17 @@ def main():
     ap.add_argument("--rays", type=int, default=96)
     ap.add_argument("--samples", type=int, default=24)
     ap.add_argument("--modes", default="oracle,hip32,hip16")
+    ap.add_argument("--deterministic", action="store_true", help="args.zest_deterministic = True in the hip modes")
+    ap.add_argument("--repeat", type=int, default=1, help="train every hip mode this many times and compare the loss curves bit for bit")
     a = ap.parse_args()
-    out = run(a.steps, a.rays, a.samples, modes=tuple(a.modes.split(",")))
-    rep = {k: out[k] for k in ("steps", "rays", "samples", "lr", "held_out_rays")}
+    out = run(a.steps, a.rays, a.samples, modes=tuple(a.modes.split(",")), deterministic=a.deterministic, repeat=a.repeat)
+    rep = {k: out[k] for k in ("steps", "rays", "samples", "lr", "held_out_rays", "deterministic", "repeat")}
     for m in a.modes.split(","):
         L = out[m]["loss"]
         rep[m] = {"loss_first": L[0], "loss_last": L[-1], "loss_every_20": [round(x, 6) for x in L[::20]],
                   "psnr_blend_db": out[m]["psnr_blend_db"], "psnr_static_db": out[m]["psnr_static_db"],
                   "psnr_train_rays_db": out[m]["psnr_train_rays_db"]}
+        rep[m].update({k: out[m][k] for k in ("repeats_identical", "first_step_that_differs") if k in out[m]})
     if "oracle" in out and "hip32" in out:
         rep["hip32_follows_oracle_steps_at_1e-3"] = follows(out["hip32"]["loss"], out["oracle"]["loss"], 1e-3)
         rep["hip32_vs_oracle_final_loss_rel"] = abs(out["hip32"]["loss"][-1] / out["oracle"]["loss"][-1] - 1.0)

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libzest_hip.so")
 SOURCES = ["capi.hip", "composite.hip", "composite_bwd.hip", "encode.hip", "rays.hip", "volume_cost.hip", "costreg.hip", "losses.hip", "sf_losses.hip", "sf_sample_losses.hip", "sf_ray_losses.hip", "patch_losses.hip", "disc.hip", "lpips.hip", "image_metrics.hip", "optim.hip", "mlp_plan.hip", "mlp.hip", "mlp_engine.hip", "mlp_train.hip", "train_gemm.hip", "mlp_train16.hip",
-           "mlp_train16_dw.hip", "fused.hip", "costreg_wgrad.hip", "costreg_dgrad.hip"]
+           "mlp_train16_dw.hip", "fused.hip", "costreg_wgrad.hip", "costreg_dgrad.hip", "det_grads.hip"]
 # per-source flags.  The engine kernels outside the fused renderer (standalone MLP, training forward, backward data and
 # finishing kernels) are built without the SLP vectorizer for the reason given at VARIANTS below (training forward
 # -5 %, data kernel -3 %, finishing -2 %); the weight-gradient kernel, a translation unit of its own, keeps it: it runs

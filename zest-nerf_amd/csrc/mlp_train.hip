@@ -9,7 +9,8 @@
 // concatenation, head activations - is fused into three small HIP kernels, the same in both modes.
 // Reproducibility with the switch on: the weight and data gradients are bit-identical from run to
 // run (fixed chunk order, no atomics); the bias gradients are NOT, in either mode - col_sums and
-// act_bwd_colsum_kernel add their per-block sums with float atomics.
+// act_bwd_colsum_kernel add their per-block sums with float atomics - unless the backward is entered through
+// zest_mlp_train_bwd_det, which sends them through per-block partials added in block order (det_grads.hip).
 //
 // Layout of one sample's saved activations (saved_per_sample floats), row-major per buffer:
 //   pre[l] = Linear_l(h) + b_l  for the D trunk layers, m = pts_bias(feats), the
@@ -20,6 +21,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include "det_grads.h"
 #include "mlp_plan.h"
 #include "train_gemm.h"
 #include "zest_common.cuh"
@@ -80,6 +82,7 @@ struct Ctx {
     float *partials;        // scratch for the split weight-gradient products
     size_t partial_floats;
     int gemm;               // ZEST_GEMM_*
+    float *bias_part;       // ordered bias sums (zest_mlp_train_bwd_det): room for the per-block partials; null: float atomics
 };
 
 // Row-major helpers on top of column-major sgemm, or on the split-bf16 kernels of train_gemm.hip.
@@ -162,6 +165,10 @@ bool gemm_dw(const Ctx &c, int M, int N, int K, const float *dY, int ldy, const 
 }
 // db[N] = column sums of dY[M,N] (ldy)
 bool col_sums(const Ctx &c, int M, int N, const float *dY, int ldy, float *db) {
+    if (c.bias_part) {
+        zest::colsum_ordered(dY, M, N, ldy, c.bias_part, db, c.st);
+        return true;
+    }
     hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, c.st, db, N);
     hipLaunchKernelGGL(colsum_kernel, dim3((M + 255) / 256), dim3(256), 0, c.st, dY, M, N, ldy, db);
     return true;
@@ -189,33 +196,26 @@ __global__ void react_kernel(const float *__restrict__ pre, const float *__restr
     act[i] = fmaxf(m ? (v2 ? p + m[i] : p * m[i]) : p, 0.f);
 }
 // d (in: dL/dact, out: dL/dpre) and dm += dL/dm, through relu(mod(pre, m)), with the bias gradient
-// folded in: db[n] += sum over the block's rows of dL/dpre.
-// One thread per column (N = 128 or 256 columns = blockDim.x), kBwdRows rows per block: the
-// separate column-sum pass over dL/dpre (11 % of a training step) disappears.
-constexpr int kBwdRows = 64;
+// folded in: db[n] += sum over the block's rows of dL/dpre, one float atomic per column and block
+// (body_act_bwd_colsum.cuh).
+using zest::kBwdRows;
 __global__ void act_bwd_colsum_kernel(float *__restrict__ d, const float *__restrict__ pre,
                                       const float *__restrict__ m, float *__restrict__ dm, int M, int N, int v2,
                                       float *__restrict__ db) {
-    const int n = threadIdx.x;
-    const int m0 = blockIdx.x * kBwdRows, m1 = min(m0 + kBwdRows, M);
-    float acc = 0.f;
-    for (int r = m0; r < m1; r++) {
-        const size_t i = (size_t)r * N + n;
-        const float p = pre[i], g = d[i];
-        float out;
-        if (!m) {
-            out = p > 0.f ? g : 0.f;
-        } else {
-            const float mv = m[i];
-            const bool on = (v2 ? p + mv : p * mv) > 0.f;
-            const float go = on ? g : 0.f;
-            out = v2 ? go : go * mv;
-            dm[i] += v2 ? go : go * p;
-        }
-        d[i] = out;
-        acc += out;
+#define ZEST_BIAS_SUM(n, acc) atomicAdd(db + n, acc)
+#include "body_act_bwd_colsum.cuh"
+#undef ZEST_BIAS_SUM
+}
+// dcur = dL/dpre in place, dm += dL/dm, db = the column sums of dL/dpre: with float atomics, or (c.bias_part) through
+// per-block partials added in block order
+void act_bwd_colsum(const Ctx &c, float *d, const float *pre, const float *m, float *dm, int M, int N, int v2, float *db) {
+    if (c.bias_part) {
+        zest::act_bwd_colsum_ordered(d, pre, m, dm, M, N, v2, c.bias_part, db, c.st);
+        return;
     }
-    atomicAdd(db + n, acc);
+    hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, c.st, db, N);
+    hipLaunchKernelGGL(act_bwd_colsum_kernel, dim3((M + kBwdRows - 1) / kBwdRows), dim3(N), 0, c.st, d, pre, m, dm, M, N,
+                       v2, db);
 }
 __global__ void fill_kernel(float *__restrict__ p, long long n, float v) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,7 +295,7 @@ extern "C" size_t zest_mlp_train_workspace_floats_ex(const zest_mlp_desc *desc, 
 static bool make_ctx(int gemm, hipStream_t st, float *workspace, int M, const Shape &s, Ctx *cx) {
     const int W = s.W;
     cx->h = gemm == ZEST_GEMM_LIBRARY ? handle_for(st) : nullptr;
-    cx->st = st, cx->gemm = gemm;
+    cx->st = st, cx->gemm = gemm, cx->bias_part = nullptr;
     cx->partials = workspace + (size_t)M * work_per_sample(W);
     cx->partial_floats = partial_floats_for(gemm, M, s);
     return gemm == ZEST_GEMM_SPLIT_BF16 || cx->h;
@@ -401,9 +401,34 @@ extern "C" int zest_mlp_train_bwd(const zest_mlp_desc *desc, const float *const 
                                  ZEST_GEMM_LIBRARY);
 }
 
+// the bias partials of the ordered sums: one row of W floats per kBwdRows rows of M, behind everything else
+static size_t bias_part_floats(int M, int W) { return (size_t)((M + kBwdRows - 1) / kBwdRows) * W; }
+
+extern "C" size_t zest_mlp_train_workspace_floats_det(const zest_mlp_desc *desc, int M, int gemm) {
+    Shape s;
+    const size_t n = zest_mlp_train_workspace_floats_ex(desc, M, gemm);
+    return n && shape_of(*desc, &s) ? n + bias_part_floats(M, s.W) : 0;
+}
+
+static int mlp_train_bwd(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
+                         const float *saved, const float *out, const float *g_out, float *workspace, float *g_x,
+                         float *const *g_params, void *stream, int gemm, bool ordered_bias);
+
 extern "C" int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *const *params, const float *x,
                                      int M, const float *saved, const float *out, const float *g_out,
                                      float *workspace, float *g_x, float *const *g_params, void *stream, int gemm) {
+    return mlp_train_bwd(desc, params, x, M, saved, out, g_out, workspace, g_x, g_params, stream, gemm, false);
+}
+
+extern "C" int zest_mlp_train_bwd_det(const zest_mlp_desc *desc, const float *const *params, const float *x,
+                                      int M, const float *saved, const float *out, const float *g_out,
+                                      float *workspace, float *g_x, float *const *g_params, void *stream, int gemm) {
+    return mlp_train_bwd(desc, params, x, M, saved, out, g_out, workspace, g_x, g_params, stream, gemm, true);
+}
+
+static int mlp_train_bwd(const zest_mlp_desc *desc, const float *const *params, const float *x, int M,
+                         const float *saved, const float *out, const float *g_out, float *workspace, float *g_x,
+                         float *const *g_params, void *stream, int gemm, bool ordered_bias) {
     ZEST_CHECK_ARG(gemm == ZEST_GEMM_LIBRARY || gemm == ZEST_GEMM_SPLIT_BF16,
                    "zest_mlp_train_bwd: gemm must be ZEST_GEMM_LIBRARY or ZEST_GEMM_SPLIT_BF16");
     if (M == 0) return 0;                       // an empty batch is a no-op (its tensors have no storage)
@@ -415,6 +440,7 @@ extern "C" int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *con
     hipStream_t st = (hipStream_t)stream;
     Ctx cx;
     ZEST_CHECK_ARG(make_ctx(gemm, st, workspace, M, s, &cx), "zest_mlp_train_bwd: cannot create a rocBLAS handle (library GEMMs)");
+    if (ordered_bias) cx.bias_part = cx.partials + cx.partial_floats;
     Params p;
     GradParams g;
     for (int i = 0; i < ZEST_P_COUNT; i++) {
@@ -439,9 +465,7 @@ extern "C" int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *con
     RB(gemm_dw(cx, M, 3, HW, dhp, 16, act, HW, g.w[ZEST_P_RGB], HW));
     RB(col_sums(cx, M, 3, dhp, 16, g.b[ZEST_P_RGB]));
     RB(gemm_dx(cx, M, 3, HW, dhp, 16, p.w[ZEST_P_RGB], HW, dhv, HW, 0.f));
-    hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, st, g.b[ZEST_P_VIEWS], HW);
-    hipLaunchKernelGGL(act_bwd_colsum_kernel, dim3((M + kBwdRows - 1) / kBwdRows), dim3(HW), 0, st, dhv, hvpre,
-                       (const float *)nullptr, (float *)nullptr, M, HW, 0, g.b[ZEST_P_VIEWS]);
+    act_bwd_colsum(cx, dhv, hvpre, nullptr, nullptr, M, HW, 0, g.b[ZEST_P_VIEWS]);
     // views_linears.0 on [feature | views]
     RB(gemm_dw(cx, M, HW, W, dhv, HW, featl, W, g.w[ZEST_P_VIEWS], W + s.V));
     RB(gemm_dw(cx, M, HW, s.V, dhv, HW, xv, s.C_in, g.w[ZEST_P_VIEWS] + W, W + s.V));
@@ -469,9 +493,7 @@ extern "C" int zest_mlp_train_bwd_ex(const zest_mlp_desc *desc, const float *con
     float *dcur = da, *dnxt = db_;
     for (int l = D - 1; l >= 0; l--) {
         // dcur = dL/dpre_l, and its column sums = the bias gradient
-        hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(256), 0, st, g.b[l], W);
-        hipLaunchKernelGGL(act_bwd_colsum_kernel, dim3((M + kBwdRows - 1) / kBwdRows), dim3(W), 0, st, dcur, pre[l],
-                           mbuf, dm, M, W, s.v2, g.b[l]);
+        act_bwd_colsum(cx, dcur, pre[l], mbuf, dm, M, W, s.v2, g.b[l]);
         if (l == 0) {
             RB(gemm_dw(cx, M, W, s.P, dcur, W, xp, s.C_in, g.w[0], s.P));
             if (g_x) RB(gemm_dx(cx, M, W, s.P, dcur, W, p.w[0], s.P, gxp, s.C_in, 1.f));

@@ -10,7 +10,8 @@
 //                   forward) and the modulation m = pts_bias(feats) (recomputed per row block with the
 //                   same 2-4 MFMA pairs as the forward) and leaves d(pre-activation) as the next
 //                   operand; those tiles also go to the gradient stash; the point-encoding rows of
-//                   layers 5 and 0 leave as float atomics into g_x.
+//                   layers 5 and 0 leave through a side buffer that the finishing kernel adds into g_x
+//                   (PtsEpi below; no atomics).
 //   modulation      d m = sum_l d pre_l * h_l / m^2 per sample from the two stashes, d features = Wm^T d m.
 //   weight kernel   d W_op = sum over samples of d pre_op (x) input_op, d b_op = sum d pre_op: stash tiles
 //                   hold samples on the lane axis, the contraction runs over samples, so the tiles are

@@ -9,13 +9,12 @@
 // taken, the running sum / sum of squares / in-frame count stay in registers, and the 3 V image
 // channels, the 32 variance channels and the V masks are written once.  Bound: the HBM write of
 // the output (41 x D x Hp x Wp floats); the source maps are a few MB and stay in L2.
-#include "zest_common.cuh"
+#include "sweep_taps.cuh"
 #include "../../include/zest_render.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kC = 32;               // feature channels of FeatureNet's top level
 
 // sum over the four lanes of a quad, result on all four: two DPP quad permutes ([1,0,3,2], [2,3,0,1]) instead of
 // the two LDS-crossbar shuffles (ds_bpermute) __shfl_xor compiles to
@@ -23,43 +22,6 @@ __device__ __forceinline__ float quad_sum(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
     return v;
-}
-
-struct Tap4 {                        // bilinear taps, zero padding, align_corners (grid_sample)
-    int off[4];                      // pixel offsets y * W + x (clamped when the weight is 0)
-    float w[4];
-};
-
-// Source-view sampling position of reference pixel (xr, yr) on the plane at `depth`, following
-// homo_warp's arithmetic: p = R [xr, yr, 1]^T + T / depth; (sx, sy) = p.xy / p.z; normalised to
-// [-1, 1] (the in-frame mask is taken on the normalised value, strictly inside) and mapped
-// back to pixels as grid_sample(align_corners=True) does.
-__device__ __forceinline__ void project(const float *__restrict__ P, float xr, float yr, float depth,
-                                        int H, int W, float &gx, float &gy) {
-    const float X = fmaf(P[0], xr, fmaf(P[1], yr, P[2])) + P[3] / depth;
-    const float Y = fmaf(P[4], xr, fmaf(P[5], yr, P[6])) + P[7] / depth;
-    const float Z = fmaf(P[8], xr, fmaf(P[9], yr, P[10])) + P[11] / depth;
-    gx = (X / Z) / ((float)(W - 1) / 2.0f) - 1.0f;
-    gy = (Y / Z) / ((float)(H - 1) / 2.0f) - 1.0f;
-}
-
-__device__ __forceinline__ Tap4 taps(float gx, float gy, int H, int W) {
-    Tap4 t;
-    float px = (gx + 1.0f) * 0.5f * (float)(W - 1), py = (gy + 1.0f) * 0.5f * (float)(H - 1);
-    // NaN / far-away positions (a plane behind the source camera): no contribution
-    const bool finite = fabsf(px) < 1e8f && fabsf(py) < 1e8f;
-    px = finite ? px : -4.0f, py = finite ? py : -4.0f;
-    const float x0f = floorf(px), y0f = floorf(py);
-    const float tx = px - x0f, ty = py - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int dx = c & 1, dy = c >> 1, xi = x0 + dx, yi = y0 + dy;
-        const bool ok = (unsigned)xi < (unsigned)W && (unsigned)yi < (unsigned)H;
-        t.w[c] = ok ? (dx ? tx : 1.0f - tx) * (dy ? ty : 1.0f - ty) : 0.0f;
-        t.off[c] = min(max(yi, 0), H - 1) * W + min(max(xi, 0), W - 1);
-    }
-    return t;
 }
 
 __global__ void nchw_to_nhwc_kernel(const float *__restrict__ in, int N, int C, long long npix,
@@ -81,9 +43,7 @@ __global__ void nchw_to_nhwc_kernel(const float *__restrict__ in, int N, int C, 
 // loads each, one 32-bit offset per tap), where a lane-per-voxel gather touches 64 lines per
 // load instruction and uses 16 bytes of each.  The 4V + 32 output values of a voxel then go through an LDS
 // tile, from which every plane receives the workgroup's 64 voxels as one 256-byte streaming store (see below).
-constexpr int kMaxViews = 8;
 constexpr int kClChannels = 48;        // channels of the channels-last cost volume (3 V + 32 = 41 for V = 3, padded to octets)
-constexpr int kRowStride = 66;      // row stride (floats) of the backward kernel's LDS transpose tile
 
 // Output path: the 4V + 32 values of the 64 voxels are transposed through a 12 KB LDS tile so that every plane
 // receives one 256-byte store per workgroup (9 workgroups per CU).  Measured on one MI355X (NSFF geometry, same
@@ -271,122 +231,21 @@ __global__ __launch_bounds__(kThreads) void homo_warp_kernel(
     }
 }
 
-// ---- backward of the plane sweep ----------------------------------------------------------
-// The trainable input of build_volume_cost is the feature maps (FeatureNet's output; the images,
-// homographies and depths are data, and the in-frame counts come from comparisons: no gradient).
-// Per voxel and channel, with a_i the (warped) feature of view i, n the in-frame count and
-// var = sum a_i^2 / n - (sum a_i / n)^2:      d var / d a_i = (2 / n) (a_i - mean).
-// The warped features are not kept by the forward pass (V-1 volumes of 350 MB each at the NSFF
-// geometry): they are gathered again here.  A workgroup is one wave and owns 64 consecutive voxels,
-// as in the forward kernel: phase 1 (lane = voxel) recomputes the homographies and bilinear taps
-// into LDS and transposes the 32 gradient planes of its voxels through LDS (each plane read as 256
-// contiguous bytes); phase 2 walks the voxels two at a time with lane = (voxel of the pair,
-// channel): a bilinear tap is one 128-byte line per voxel, read - and scattered back with float
-// atomics - by 32 neighbouring lanes, the access shape at which memory-side float atomics run at
-// full rate (MI355X_MICROARCH.md, Global float atomics: two 128-B segments per wave-instruction).
-// feats_cl [V,H,W,32], g_img_feat [3V+32, D, Hp, Wp] (only its last 32 channels are read),
-// g_feats_cl [V,H,W,32] accumulated (zero it first).
+// ---- backward of the plane sweep and of homo_warp (body_volume_cost_bwd.cuh, body_homo_warp_bwd.cuh), the
+// contributions added with float atomics.  g_feats_cl and g_src are accumulated: zero them first.
 template <int VT>
 __global__ __launch_bounds__(64) void volume_cost_bwd_kernel(
     const float *__restrict__ feats, const float *__restrict__ proj, const float *__restrict__ depth, int V_rt,
     int D, int H, int W, int pad, const float *__restrict__ g_img_feat, float *__restrict__ g_feats) {
-    const int V = VT > 0 ? VT : V_rt;
-    constexpr int VM = VT > 0 ? VT : kMaxViews;
-    __shared__ float gt[kC * kRowStride];                      // gradient of the variance planes [channel][voxel]
-    __shared__ int4 toff[(VM - 1) * 64];
-    __shared__ float4 tw[(VM - 1) * 64];
-    __shared__ float2 vox[64];                                  // ref pixel offset (-1: none), 1/count
-    const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-    const long long nvox = (long long)D * Hp * Wp;
-    const int lane = threadIdx.x;
-    const long long base = (long long)blockIdx.x * 64;
-    {   // ---- phase 1: lane = voxel
-        const long long idx = base + lane;
-        const bool live = idx < nvox;
-        const unsigned ic = (unsigned)(live ? idx : nvox - 1);
-        const unsigned row = ic / (unsigned)Wp;
-        const int x = (int)(ic - row * (unsigned)Wp), d = (int)(row / (unsigned)Hp), y = (int)(row - (unsigned)d * (unsigned)Hp);
-        const int xr = x - pad, yr = y - pad;
-        const bool inside = (unsigned)xr < (unsigned)W && (unsigned)yr < (unsigned)H;
-        const float dep = depth[d];
-        float count = 1.0f;
-#pragma unroll
-        for (int i = 1; i < V; i++) {
-            float gx, gy;
-            project(proj + 12 * (i - 1), (float)xr, (float)yr, dep, H, W, gx, gy);
-            count += (gx > -1.0f && gx < 1.0f && gy > -1.0f && gy < 1.0f) ? 1.0f : 0.0f;
-            const Tap4 t = taps(gx, gy, H, W);
-            toff[(i - 1) * 64 + lane] = make_int4(t.off[0], t.off[1], t.off[2], t.off[3]);
-            // a voxel past the end of the volume scatters nothing
-            tw[(i - 1) * 64 + lane] = live ? make_float4(t.w[0], t.w[1], t.w[2], t.w[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        vox[lane] = make_float2(__int_as_float(live && inside ? yr * W + xr : -1), 1.0f / count);
-        const size_t plane0 = (size_t)(3 * V) * nvox;
-        for (int c = 0; c < kC; c++)
-            gt[c * kRowStride + lane] = live ? g_img_feat[plane0 + (size_t)c * nvox + idx] : 0.0f;
-    }
-    __syncthreads();
-    // ---- phase 2: lane = (voxel of a pair, channel)
-    const int c = lane & 31, vp = lane >> 5;
-    const size_t HW = (size_t)H * W;
-    for (int it = 0; it < 32; it++) {
-        const int v = 2 * it + vp;
-        const float2 gv = vox[v];
-        const int ref_off = __float_as_int(gv.x);
-        const float g = gt[c * kRowStride + v], inv = gv.y;
-        float a[VM];
-        a[0] = ref_off >= 0 ? feats[(size_t)ref_off * kC + c] : 0.0f;
-        float sum = a[0];
-#pragma unroll
-        for (int i = 1; i < V; i++) {
-            const int4 o4 = toff[(i - 1) * 64 + v];
-            const float4 w4 = tw[(i - 1) * 64 + v];
-            const float *f = feats + (size_t)i * HW * kC + c;
-            a[i] = fmaf(w4.w, f[(size_t)o4.w * kC], fmaf(w4.z, f[(size_t)o4.z * kC],
-                        fmaf(w4.y, f[(size_t)o4.y * kC], w4.x * f[(size_t)o4.x * kC])));
-            sum += a[i];
-        }
-        const float mean = sum * inv, k = 2.0f * inv * g;
-        if (ref_off >= 0) atomicAdd(g_feats + (size_t)ref_off * kC + c, k * (a[0] - mean));
-#pragma unroll
-        for (int i = 1; i < V; i++) {
-            const int4 o4 = toff[(i - 1) * 64 + v];
-            const float4 w4 = tw[(i - 1) * 64 + v];
-            float *gf = g_feats + (size_t)i * HW * kC + c;
-            const float ga = k * (a[i] - mean);
-            // wave-uniform per half: a tap with weight 0 (outside the frame) is skipped by all 32 lanes
-            if (w4.x != 0.0f) atomicAdd(gf + (size_t)o4.x * kC, w4.x * ga);
-            if (w4.y != 0.0f) atomicAdd(gf + (size_t)o4.y * kC, w4.y * ga);
-            if (w4.z != 0.0f) atomicAdd(gf + (size_t)o4.z * kC, w4.z * ga);
-            if (w4.w != 0.0f) atomicAdd(gf + (size_t)o4.w * kC, w4.w * ga);
-        }
-    }
+#define ZEST_GRAD_ADD(p, v) atomicAdd(p, v)
+#include "body_volume_cost_bwd.cuh"
 }
 
-// backward of homo_warp with respect to the source map: g_warped [C,D,Hp,Wp] -> g_src [C,H,W]
-// (accumulated: zero it first).  The sampling positions (grid or homography + depths) are data.
 __global__ __launch_bounds__(kThreads) void homo_warp_bwd_kernel(
     const float *__restrict__ proj, const float *__restrict__ depth, const float *__restrict__ grid_in, int C, int D,
     int H, int W, int Hp, int Wp, int pad, const float *__restrict__ g_warped, float *__restrict__ g_src) {
-    const long long nvox = (long long)D * Hp * Wp;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nvox) return;
-    float gx, gy;
-    if (grid_in) {
-        gx = grid_in[2 * idx], gy = grid_in[2 * idx + 1];
-    } else {
-        const unsigned row = (unsigned)idx / (unsigned)Wp;
-        const int x = (int)((unsigned)idx - row * (unsigned)Wp), d = (int)(row / (unsigned)Hp), y = (int)(row - (unsigned)d * (unsigned)Hp);
-        project(proj, (float)(x - pad), (float)(y - pad), depth[d], H, W, gx, gy);
-    }
-    const Tap4 t = taps(gx, gy, H, W);
-    for (int c = 0; c < C; c++) {
-        const float g = g_warped[(size_t)c * nvox + idx];
-        float *s = g_src + (size_t)c * H * W;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (t.w[k] != 0.0f) atomicAdd(s + t.off[k], t.w[k] * g);
-    }
+#include "body_homo_warp_bwd.cuh"
+#undef ZEST_GRAD_ADD
 }
 
 }  // namespace

@@ -15,6 +15,11 @@ MLP).  Gradients exist exactly where the reference's training graph has them (SU
 Two training modes of the MLP: fp32 (MlpFn: rocBLAS sgemm + fused elementwise kernels, the 1e-3 parity
 mode; `--precision 32`) and bf16 on the hand-written MFMA kernels (MlpFn16; `--precision 16`).  The other
 stages compute in fp32 in both.
+
+Reproducibility: four of these backward passes add floats with atomics by default (the volume gradient of EncodeFn /
+EncodePairFn, VolumeCostFn, HomoWarpFn, the bias gradients of MlpFn).  With `deterministic` (renderer._Views.deterministic,
+the Functions' own argument; args.zest_deterministic / ZEST_DETERMINISTIC=1 upstream) they take the order-independent
+forms of csrc/det_grads.hip.
 """
 import torch
 from torch.autograd import Function
@@ -56,7 +61,8 @@ class EncodeFn(Function):
         v = ctx.views
         want_vol = v.vol_cl is not None and ctx.needs_input_grad[1]
         V = v.imgs_cl.shape[0] if v.imgs_cl is not None else 0
-        g_ndc, g_vol_cl = zest_hip.encode_bwd(g_x.contiguous(), ndc, ctx.t, v.vol_cl, V, want_vol)
+        g_ndc, g_vol_cl = zest_hip.encode_bwd(g_x.contiguous(), ndc.contiguous(), ctx.t, v.vol_cl, V, want_vol,
+                                              deterministic=getattr(v, "deterministic", False))
         return g_ndc, g_vol_cl, None, None, None, None
 
 
@@ -83,8 +89,10 @@ class EncodePairFn(Function):
         want_vol = v.vol_cl is not None and ctx.needs_input_grad[2]
         V = v.imgs_cl.shape[0] if v.imgs_cl is not None else 0
         g_x = g_x.contiguous()
-        g_a, g_vol_cl = zest_hip.encode_bwd(g_x[:R], ndc_a, ctx.t[0], v.vol_cl, V, want_vol)
-        g_b, g_vol_cl = zest_hip.encode_bwd(g_x[R:], ndc_b, ctx.t[1], v.vol_cl, V, want_vol, g_vol=g_vol_cl)
+        det = getattr(v, "deterministic", False)
+        g_a, g_vol_cl = zest_hip.encode_bwd(g_x[:R], ndc_a.contiguous(), ctx.t[0], v.vol_cl, V, want_vol, deterministic=det)
+        g_b, g_vol_cl = zest_hip.encode_bwd(g_x[R:], ndc_b.contiguous(), ctx.t[1], v.vol_cl, V, want_vol, g_vol=g_vol_cl,
+                                            deterministic=det)
         return g_a, g_b, g_vol_cl, None, None, None, None, None
 
 
@@ -104,14 +112,14 @@ def _slot_grads(slots, grads):
 
 class MlpFn(Function):
     @staticmethod
-    def forward(ctx, x, desc, slots, gemm, *params):
+    def forward(ctx, x, desc, slots, gemm, deterministic, *params):
         """params: the (weight, bias) tensors of the slots in `slots` (ZEST_P_* order).  gemm: zest_hip.GEMM_*, the
-        kind of GEMM forward and backward run on."""
+        kind of GEMM forward and backward run on.  deterministic: the bias gradients through ordered partials."""
         table = _param_table(slots, params)
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         out, saved = zest_hip.mlp_train_fwd(desc, table, x2, gemm=gemm)
-        ctx.desc, ctx.slots, ctx.lead, ctx.gemm = desc, slots, lead, gemm
+        ctx.desc, ctx.slots, ctx.lead, ctx.gemm, ctx.deterministic = desc, slots, lead, gemm, bool(deterministic)
         ctx.save_for_backward(x2, saved, out, *params)
         return out.view(*lead, desc.out_ch)
 
@@ -121,8 +129,9 @@ class MlpFn(Function):
         table = _param_table(ctx.slots, params)
         g_x, grads = zest_hip.mlp_train_bwd(ctx.desc, table, x2, saved, out,
                                             g_out.reshape(-1, ctx.desc.out_ch).contiguous(),
-                                            want_gx=ctx.needs_input_grad[0], gemm=ctx.gemm)
-        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, None,
+                                            want_gx=ctx.needs_input_grad[0], gemm=ctx.gemm,
+                                            deterministic=ctx.deterministic)
+        return (g_x.view(*ctx.lead, -1) if g_x is not None else None, None, None, None, None,
                 *_slot_grads(ctx.slots, grads))
 
 
@@ -251,13 +260,14 @@ def split_last(raw, sizes):
     return raw.split(sizes, -1)
 
 
-def mlp_apply(net, x, time_codes=None, bf16=False, shared=None, gemm=zest_hip.GEMM_LIBRARY):
+def mlp_apply(net, x, time_codes=None, bf16=False, shared=None, gemm=zest_hip.GEMM_LIBRARY, deterministic=False):
     """Training forward of a zest networks.MVSNeRF on x [..., C_in] with autograd.  time_codes: the
     frame's latent code for a net with time-code channels (folded into layer 0 / 5 biases with
     differentiable torch ops: gradients reach the code and the full-width weights).  bf16: the fast
     training mode (MlpFn16, 'v0' nets); otherwise the fp32 parity path (MlpFn), whose GEMMs run on
     `gemm` (zest_hip.GEMM_LIBRARY: rocBLAS sgemm; GEMM_SPLIT_BF16: the three-term bf16 MFMA kernels).  shared: see
-    MlpFn16."""
+    MlpFn16.  deterministic: the fp32 path's bias gradients through ordered partials (the bf16 kernels add nothing with
+    float atomics and need no switch)."""
     mod = net.nerf
     desc = mod._desc()
     named = mod.effective_parameters(time_codes)
@@ -277,7 +287,7 @@ def mlp_apply(net, x, time_codes=None, bf16=False, shared=None, gemm=zest_hip.GE
         warnings.warn("zest: --precision 16 training of a %s net takes the fp32 training path (rocBLAS sgemm): the "
                       "bf16 MFMA training kernels cover 'v0' nets of depth 8 / width 256 / skips [4]"
                       % ("'v2'" if desc.net_type else "D=%d W=%d" % (desc.D, desc.W)), stacklevel=2)
-    return MlpFn.apply(x, desc, tuple(slots), gemm, *params)
+    return MlpFn.apply(x, desc, tuple(slots), gemm, bool(deterministic), *params)
 
 
 class VolumeCostFn(Function):
@@ -286,9 +296,9 @@ class VolumeCostFn(Function):
     under autograd gives the same: the masks are comparisons, the grid depends on cameras only)."""
 
     @staticmethod
-    def forward(ctx, feats, imgs_lr, proj, depth, pad):
+    def forward(ctx, feats, imgs_lr, proj, depth, pad, deterministic=False):
         img_feat, masks, fcl = zest_hip.volume_cost(feats, imgs_lr, proj, depth, pad, return_feats_cl=True)
-        ctx.pad = pad
+        ctx.pad, ctx.deterministic = pad, bool(deterministic)
         ctx.save_for_backward(fcl, proj, depth)
         ctx.mark_non_differentiable(masks)
         return img_feat, masks
@@ -296,16 +306,21 @@ class VolumeCostFn(Function):
     @staticmethod
     def backward(ctx, g_img_feat, g_masks):
         fcl, proj, depth = ctx.saved_tensors
-        return zest_hip.volume_cost_bwd(fcl, proj, depth, ctx.pad, g_img_feat.contiguous()), None, None, None, None
+        if ctx.deterministic:
+            g = zest_hip.volume_cost_bwd(fcl, proj.float().contiguous(), depth.float().contiguous(), ctx.pad,
+                                         g_img_feat.float().contiguous(), deterministic=True)
+        else:
+            g = zest_hip.volume_cost_bwd(fcl, proj, depth, ctx.pad, g_img_feat.contiguous())
+        return g, None, None, None, None, None
 
 
 class HomoWarpFn(Function):
     """utils.homo_warp with respect to the source map (the sampling positions are data)."""
 
     @staticmethod
-    def forward(ctx, src, proj, depth, grid, pad):
+    def forward(ctx, src, proj, depth, grid, pad, deterministic=False):
         warped, grid_out = zest_hip.homo_warp(src, proj, depth, grid, pad)
-        ctx.pad, ctx.shape = pad, tuple(src.shape)
+        ctx.pad, ctx.shape, ctx.deterministic = pad, tuple(src.shape), bool(deterministic)
         ctx.save_for_backward(grid_out)
         ctx.mark_non_differentiable(grid_out)
         return warped, grid_out
@@ -313,7 +328,9 @@ class HomoWarpFn(Function):
     @staticmethod
     def backward(ctx, g_warped, g_grid):
         (grid,) = ctx.saved_tensors
-        return zest_hip.homo_warp_bwd(g_warped.contiguous(), ctx.shape, grid=grid, pad=ctx.pad), None, None, None, None
+        g_warped = g_warped.float().contiguous() if ctx.deterministic else g_warped.contiguous()
+        return (zest_hip.homo_warp_bwd(g_warped, ctx.shape, grid=grid, pad=ctx.pad, deterministic=ctx.deterministic),
+                None, None, None, None, None)
 
 
 class DistortionFn(Function):

@@ -132,6 +132,10 @@ _SIGS = {
     "zest_costreg_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "zest_volume_cost_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "zest_volume_cost_bwd_det_work_bytes": (_sz, [_i, _i, _i]),
+    "zest_volume_cost_bwd_det": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "zest_homo_warp_bwd_det_work_bytes": (_sz, [_i, _i, _i]),
+    "zest_homo_warp_bwd_det": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "zest_volume_lookup_fwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "zest_color_lookup_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "zest_encode_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _i, _i, _vp, _i, _i, _i,
@@ -146,6 +150,8 @@ _SIGS = {
     "zest_composite_blend_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp]),
     "zest_encode_bwd": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "zest_encode_bwd_det_work_bytes": (_sz, [_i, _i, _i]),
+    "zest_encode_bwd_det": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "zest_volume_from_cl": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "zest_mlp_train_saved_floats": (_sz, [C.POINTER(MlpDesc), _i]),
     "zest_mlp_train_workspace_floats": (_sz, [C.POINTER(MlpDesc), _i]),
@@ -156,6 +162,11 @@ _SIGS = {
     "zest_mlp_train_fwd_ex": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "zest_mlp_train_bwd_ex": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                    C.POINTER(_vp), _vp, _i]),
+    "zest_mlp_train_workspace_floats_det": (_sz, [C.POINTER(MlpDesc), _i, _i]),
+    "zest_mlp_train_bwd_det": (_i, [C.POINTER(MlpDesc), C.POINTER(_vp), _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                    C.POINTER(_vp), _vp, _i]),
+    "zest_colsum_ordered_work_floats": (_sz, [_i, _i]),
+    "zest_colsum_ordered": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "zest_train_gemm_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "zest_train_gemm_chunk_rows": (_i, []),
     "zest_train_gemm": (_i, [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp]),
@@ -1298,9 +1309,57 @@ def costreg_out(raw_a, pre_a, raw_b, pre_b):
     return out
 
 
-def volume_cost_bwd(feats_cl, proj, depth, pad, g_img_feat):
+# ---- the order-independent forms of the scatter-add gradients (deterministic=True; include/zest_render.h, *_det) ----
+DET_MAX_CONTRIBUTIONS = 1 << 32
+
+
+def _det_operands(who, operands):
+    """The *_det calls take their operands as they are - (name, tensor, shape with None for any extent): contiguous fp32
+    tensors of those shapes, checked before the device (the C ABI sees pointers and sizes only) - and then on one HIP
+    device, which is returned."""
+    for nm, t, shape in operands:
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != len(shape)
+                or any(w is not None and int(w) != g for w, g in zip(shape, t.shape))):
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s" % (
+                who, nm, tuple("*" if w is None else int(w) for w in shape),
+                "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous()) if torch.is_tensor(t) else type(t).__name__))
+    return operands[0][1].device
+
+
+def _det_checked(who, operands, work, nbytes, n_contrib, what):
+    """Operands, workspace and the number of contributions of a *_det call, every refusal before the device is looked at.
+    -> the workspace (the caller's, or a fresh one)."""
+    dev = _det_operands(who, operands)
+    if nbytes == 0:
+        _check(1, who)
+    if work is not None and (not torch.is_tensor(work) or work.dtype != torch.uint8 or not work.is_contiguous()
+                             or work.numel() != nbytes or work.data_ptr() % 16):
+        raise RuntimeError("%s: work must be %d contiguous uint8 elements, 16-byte aligned" % (who, nbytes))
+    if n_contrib > DET_MAX_CONTRIBUTIONS:
+        raise RuntimeError("%s: %d contributions (%s) exceed 2^32" % (who, n_contrib, what))
+    for nm, t in [(o[0], o[1]) for o in operands] + ([("work", work)] if work is not None else []):
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (all tensors on one)" % (who, nm, t.device))
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8) if work is None else work
+
+
+def volume_cost_bwd(feats_cl, proj, depth, pad, g_img_feat, deterministic=False, work=None):
     """g_img_feat [3V+32, D, Hp, Wp] -> gradient of the feature maps [V,32,H,W] (a channels-first view of
-    the channels-last buffer the kernel scatters into)."""
+    the channels-last buffer the kernel scatters into).  deterministic: the order-independent form
+    (zest_volume_cost_bwd_det; contiguous fp32 operands; work: zest_volume_cost_bwd_det_work_bytes(V, H, W) uint8
+    elements to reuse, 16-byte aligned)."""
+    if deterministic:
+        who = "zest_hip.volume_cost_bwd(deterministic)"
+        V, H, W, Cc = feats_cl.shape if torch.is_tensor(feats_cl) and feats_cl.dim() == 4 else (0, 0, 0, 0)
+        D, pad = (int(depth.shape[0]) if torch.is_tensor(depth) and depth.dim() == 1 else 0), int(pad)
+        ops = (("feats_cl", feats_cl, (None, None, None, 32)), ("g_img_feat", g_img_feat, (3 * V + Cc, D, H + 2 * pad, W + 2 * pad)),
+               ("proj_mats", proj, (V - 1, 3, 4)), ("depth_values", depth, (None,)))
+        work = _det_checked(who, ops, work, int(lib().zest_volume_cost_bwd_det_work_bytes(V, H, W)),
+                            D * (H + 2 * pad) * (W + 2 * pad) * V * 4, "voxels x views x 4 taps")
+        g = torch.empty_like(feats_cl)
+        _check(lib().zest_volume_cost_bwd_det(_ptr(feats_cl), _ptr(proj), _ptr(depth), V, Cc, D, H, W, pad, _ptr(g_img_feat),
+                                              _ptr(g), _ptr(work), _stream(feats_cl)), "zest_volume_cost_bwd_det")
+        return g.permute(0, 3, 1, 2)
     g_img_feat, proj, depth = _dev(g_img_feat, "g_img_feat"), _dev(proj, "proj_mats"), _dev(depth, "depth_values")
     V, H, W, Cc = feats_cl.shape
     D = depth.shape[0]
@@ -1313,8 +1372,23 @@ def volume_cost_bwd(feats_cl, proj, depth, pad, g_img_feat):
     return g.permute(0, 3, 1, 2)
 
 
-def homo_warp_bwd(g_warped, src_shape, proj=None, depth=None, grid=None, pad=0):
-    """g_warped [C,D,Hp,Wp] -> g_src [C,H,W]; grid [D,Hp,Wp,2] or proj [3,4] + depth [D] as in homo_warp."""
+def homo_warp_bwd(g_warped, src_shape, proj=None, depth=None, grid=None, pad=0, deterministic=False, work=None):
+    """g_warped [C,D,Hp,Wp] -> g_src [C,H,W]; grid [D,Hp,Wp,2] or proj [3,4] + depth [D] as in homo_warp.
+    deterministic: the order-independent form (zest_homo_warp_bwd_det; contiguous fp32 operands; work:
+    zest_homo_warp_bwd_det_work_bytes(C, H, W) uint8 elements to reuse, 16-byte aligned)."""
+    if deterministic:
+        who = "zest_hip.homo_warp_bwd(deterministic)"
+        Cc, H, W = (int(v) for v in src_shape)
+        D, Hp, Wp = g_warped.shape[1:] if torch.is_tensor(g_warped) and g_warped.dim() == 4 else (0, 0, 0)
+        ops = (("g_warped", g_warped, (Cc, None, None, None)),)
+        ops += (("src_grid", grid, (D, Hp, Wp, 2)),) if grid is not None else (("proj_mat", proj, (3, 4)), ("depth_values", depth, (D,)))
+        work = _det_checked(who, ops, work, int(lib().zest_homo_warp_bwd_det_work_bytes(Cc, H, W)), D * Hp * Wp * 4,
+                            "voxels x 4 taps")
+        g = torch.empty(Cc, H, W, device=g_warped.device, dtype=torch.float32)
+        proj, depth = (None, None) if grid is not None else (proj, depth)
+        _check(lib().zest_homo_warp_bwd_det(_ptr(proj), _ptr(depth), _ptr(grid), Cc, D, H, W, Hp, Wp, int(pad), _ptr(g_warped),
+                                            _ptr(g), _ptr(work), _stream(g_warped)), "zest_homo_warp_bwd_det")
+        return g
     g_warped = _dev(g_warped, "g_warped")
     Cc, H, W = src_shape
     D, Hp, Wp = g_warped.shape[1:]
@@ -1490,9 +1564,25 @@ def composite_blend_bwd(raw_dy, raw_st, blend, z, rays_dir, noise, noise_std, g_
 
 
 # ------------------------------------------------------------------- training path (backward)
-def encode_bwd(g_x, ndc, t, vol_cl, V, want_vol_grad, g_vol=None):
+def encode_bwd(g_x, ndc, t, vol_cl, V, want_vol_grad, g_vol=None, deterministic=False, work=None):
     """-> g_ndc [R,S,3], g_vol_cl [H,W,D,8] or None.  g_vol: an existing volume gradient to add into (the kernel
-    scatter-adds) instead of a fresh zero-filled one."""
+    scatter-adds) instead of a fresh zero-filled one.  deterministic: the volume gradient through the order-independent
+    form (zest_encode_bwd_det; contiguous fp32 operands; work: zest_encode_bwd_det_work_bytes(D, Hv, Wv) uint8 elements
+    to reuse, 16-byte aligned); a g_vol given is then added to with one elementwise launch.  Without a volume gradient
+    nothing is added up and the mode changes nothing."""
+    if deterministic and vol_cl is not None and want_vol_grad:
+        who = "zest_hip.encode_bwd(deterministic)"
+        R, S = ndc.shape[:2] if torch.is_tensor(ndc) and ndc.dim() == 3 else (0, 0)
+        Hv, Wv, D = vol_cl.shape[:3] if torch.is_tensor(vol_cl) and vol_cl.dim() == 4 else (0, 0, 0)
+        c_in = (4 if t is not None else 3) * 21 + 8 + 4 * int(V) + 27
+        ops = (("ndc", ndc, (None, None, 3)), ("g_x", g_x, (R, S, c_in)), ("vol_cl", vol_cl, (None, None, None, 8)))
+        ops += (("g_vol", g_vol, (Hv, Wv, D, 8)),) if g_vol is not None else ()
+        work = _det_checked(who, ops, work, int(lib().zest_encode_bwd_det_work_bytes(D, Hv, Wv)), R * S * 8, "R S 8")
+        g_ndc, g_new = torch.empty_like(ndc), torch.empty_like(vol_cl)
+        _check(lib().zest_encode_bwd_det(_ptr(g_x), _ptr(ndc), R, S, int(t is not None), float(t) if t is not None else 0.0,
+                                         _ptr(vol_cl), D, Hv, Wv, int(V), _ptr(g_ndc), _ptr(g_new), _ptr(work), _stream(ndc)),
+               "zest_encode_bwd_det")
+        return g_ndc, (g_new if g_vol is None else g_vol.add_(g_new))
     ndc = _dev(ndc, "ndc", (None, None, 3))
     R, S, _ = ndc.shape
     c_in = (4 if t is not None else 3) * 21 + (8 + 4 * int(V) if vol_cl is not None else 0) + 27
@@ -1629,6 +1719,20 @@ def train_gemm(gemm, op, a, b, c=None, beta=0.0):
     return c
 
 
+def colsum_ordered(a):
+    """Column sums of a [M,N] (N <= 256, rows contiguous, any row stride) the way the deterministic backward of the fp32
+    training path forms its bias gradients: per-block partials added in block order.  -> [N] fp32."""
+    a, lda = _gemm_operand(a, "a")
+    M, N = a.shape
+    L = lib()
+    n = int(L.zest_colsum_ordered_work_floats(M, N))
+    if n == 0:
+        _check(1, "zest_colsum_ordered_work_floats")
+    work, out = torch.empty(n, device=a.device), torch.empty(N, device=a.device)
+    _check(L.zest_colsum_ordered(_ptr(a), M, N, lda, _ptr(work), _ptr(out), _stream(a)), "zest_colsum_ordered")
+    return out
+
+
 def mlp_train_fwd(desc, params, x, gemm=GEMM_LIBRARY):
     """params: 2*P_COUNT tensors-or-None.  -> out [M,C_out], saved (opaque activation stash).
     gemm: GEMM_LIBRARY (rocBLAS sgemm) or GEMM_SPLIT_BF16 (three-term bf16 MFMA kernels)."""
@@ -1645,8 +1749,10 @@ def mlp_train_fwd(desc, params, x, gemm=GEMM_LIBRARY):
     return out, saved
 
 
-def mlp_train_bwd(desc, params, x, saved, out, g_out, want_gx=True, gemm=GEMM_LIBRARY):
-    """-> g_x [.., C_in] or None, list of 2*P_COUNT parameter gradients (None where absent)."""
+def mlp_train_bwd(desc, params, x, saved, out, g_out, want_gx=True, gemm=GEMM_LIBRARY, deterministic=False):
+    """-> g_x [.., C_in] or None, list of 2*P_COUNT parameter gradients (None where absent).  deterministic: the bias
+    gradients through ordered partials instead of float atomics (zest_mlp_train_bwd_det); with GEMM_SPLIT_BF16 every
+    gradient then has the same bits on every call (the library's GEMMs are rocBLAS's to answer for)."""
     gemm = _gemm_kind(gemm)
     x = _mlp_rows(desc, x)
     M = x.numel() // x.shape[-1]
@@ -1654,12 +1760,14 @@ def mlp_train_bwd(desc, params, x, saved, out, g_out, want_gx=True, gemm=GEMM_LI
     L = lib()
     if saved.numel() < int(L.zest_mlp_train_saved_floats(C.byref(desc), M)):
         raise RuntimeError("zest_hip: `saved` is not the stash of this forward call (too small)")
-    work = torch.empty(int(L.zest_mlp_train_workspace_floats_ex(C.byref(desc), M, gemm)), device=x.device)
+    floats, bwd = ((L.zest_mlp_train_workspace_floats_det, L.zest_mlp_train_bwd_det) if deterministic else
+                   (L.zest_mlp_train_workspace_floats_ex, L.zest_mlp_train_bwd_ex))
+    work = torch.empty(int(floats(C.byref(desc), M, gemm)), device=x.device)
     keep = _params(desc, params)
     grads = [(torch.empty_like(p) if p is not None else None) for p in keep]
     g_x = torch.empty_like(x) if want_gx else None
-    _check(L.zest_mlp_train_bwd_ex(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(out), _ptr(g_out),
-                                   _ptr(work), _ptr(g_x), _ptr_table(grads), _stream(x), gemm), "zest_mlp_train_bwd")
+    _check(bwd(C.byref(desc), _ptr_table(keep), _ptr(x), M, _ptr(saved), _ptr(out), _ptr(g_out),
+               _ptr(work), _ptr(g_x), _ptr_table(grads), _stream(x), gemm), "zest_mlp_train_bwd")
     return g_x, grads
 
 
@@ -1702,7 +1810,8 @@ def mlp_train16_bwd(desc, packed_bwd, params, x, stash, out, g_out, stages=7, wo
     if work is None or work.numel() < need:
         work = torch.empty(need, device=x.device, dtype=torch.uint8)
     keep = _params(desc, params)
-    # the gradients are accumulated with atomics: one zero-filled buffer (one fill launch), views into it
+    # the weight kernel adds its totals into the gradients (ordered partials, no atomics): one zero-filled buffer (one
+    # fill launch), views into it
     sizes = [(p.numel() + 3) // 4 * 4 if p is not None else 0 for p in keep]
     flat = torch.zeros(sum(sizes), device=x.device, dtype=torch.float32)
     grads, off = [], 0

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 import zest_hip
 
-__all__ = ["Embedding", "Renderer", "Renderer_linear", "MVSNeRF", "resolve_precision", "inference_precision", "train_gemm_choice",
+__all__ = ["Embedding", "Renderer", "Renderer_linear", "MVSNeRF", "resolve_precision", "inference_precision", "train_gemm_choice", "deterministic_choice",
            "ActivatedBatchNorm", "ConvBnReLU", "ConvBnReLU3D", "FeatureNet", "CostRegNet", "MVSNet",
            "MVSNeRF_G", "DyMVSNeRF_G", "GRAFDiscriminator"]
 
@@ -71,6 +71,27 @@ def train_gemm_choice(args=None, train16=False):
             _warned_train_gemm16 = True
         return zest_hip.GEMM_LIBRARY
     return zest_hip.GEMM_NAMES[name]
+
+
+def deterministic_choice(args=None):
+    """-> bool: the opt-in switch for bit-reproducible gradients, from the environment variable ZEST_DETERMINISTIC
+    ("1" or "0": it overrides the argument), else args.zest_deterministic, else off.  With it on, the four places of the
+    training path that add floats with atomics - the gradient of the encoding volume (zest_encode_bwd), of the feature
+    maps through the plane sweep (zest_volume_cost_bwd) and through utils.homo_warp, and the bias gradients of the fp32
+    MLP path - take order-independent forms (csrc/det_grads.hip), so that no gradient the project's own kernels produce
+    depends on the order in which workgroups arrive; off, every result keeps its bits and its speed.  rendering() reads
+    it once per call, _Generator._volume hands it to the builder (MVSNet.zest_deterministic).
+    Complete reproducibility of the fp32 rendering path needs zest_train_gemm = "split" as well: behind the default
+    "library" the GEMMs are rocBLAS's, whose summation order the project does not control.  The library's convolution
+    backward in the volume builder (layers 1-9 of the regularisation net, the feature pyramid) is outside the switch too.
+    A non-finite gradient poisons the whole result of a scatter-add in this mode, where the default poisons the
+    elements it touches."""
+    env = os.environ.get("ZEST_DETERMINISTIC", "")
+    if env:
+        if env not in ("0", "1"):
+            raise ValueError("zest: ZEST_DETERMINISTIC must be 0 or 1, got %r" % (env,))
+        return env == "1"
+    return bool(getattr(args, "zest_deterministic", False))
 
 
 def inference_precision(prec, args=None):
@@ -362,7 +383,8 @@ class MVSNeRF(nn.Module):
         if self.nerf.in_ch_time == 0 and torch.is_grad_enabled() and (
                 x.requires_grad or any(p.requires_grad for p in self.parameters())):
             import zest_autograd
-            return zest_autograd.mlp_apply(self, x, gemm=train_gemm_choice())     # fp32 training path (HIP fwd + bwd)
+            return zest_autograd.mlp_apply(self, x, gemm=train_gemm_choice(),     # fp32 training path (HIP fwd + bwd)
+                                           deterministic=deterministic_choice())
         return self.nerf(x)
 
 
@@ -674,6 +696,9 @@ class MVSNet(nn.Module):
         # opt-in, likewise: the data gradient of cost_reg_2.conv0 - the gradient towards the cost volume - from the HIP
         # kernel, as fp32 channel planes (nothing extra is kept for it).  No effect in fp32 mode.
         self.zest_hip_costreg_dgrad = False
+        # opt-in (args.zest_deterministic / ZEST_DETERMINISTIC=1, see deterministic_choice): the gradient towards the
+        # feature maps through the order-independent plane-sweep backward instead of float atomics
+        self.zest_deterministic = False
 
     def build_volume_cost(self, imgs, feats, proj_mats, depth_values, pad=0):
         """imgs [1,V,3,Hi,Wi]; feats [1,V,32,H,W]; proj_mats [1,V,3,4]; depth_values [1,D]
@@ -689,7 +714,8 @@ class MVSNet(nn.Module):
         if torch.is_grad_enabled() and feats.requires_grad:
             import zest_autograd
             img_feat, masks = zest_autograd.VolumeCostFn.apply(feats[0].float(), imgs_lr.detach(), proj_mats[0, 1:].detach(),
-                                                               depth.detach(), pad)
+                                                               depth.detach(), pad,
+                                                               bool(getattr(self, "zest_deterministic", False)))
         else:
             img_feat, masks = zest_hip.volume_cost(feats[0], imgs_lr, proj_mats[0, 1:], depth, pad)
         return img_feat[None], masks[None]
@@ -800,9 +826,11 @@ class _Generator(nn.Module):
             if (not train and getattr(self.args, "zest_graph_builders", True) and isinstance(net, MVSNet)
                     and net.feature.hip_supported() and net.hip_path(imgs, self.args.pad)):
                 return self._volume_replayed(net, imgs, proj_mats, near_far)
-            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad"):
+            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad", "zest_deterministic"):
                 if train and isinstance(net, MVSNet) and getattr(self.args, name, None) is not None:
                     setattr(net, name, bool(getattr(self.args, name)))      # the caller's choice, else MVSNet's default
+            if train and isinstance(net, MVSNet) and os.environ.get("ZEST_DETERMINISTIC", ""):
+                net.zest_deterministic = deterministic_choice(self.args)    # the environment overrides the argument
             return net(imgs, proj_mats, near_far, pad=self.args.pad)[0].float()
 
     def _volume_replayed(self, net, imgs, proj_mats, near_far):

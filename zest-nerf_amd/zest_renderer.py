@@ -20,7 +20,7 @@ Two execution plans:
 import torch
 
 import zest_hip
-from zest_networks import MVSNeRF, inference_precision, resolve_precision, train_gemm_choice
+from zest_networks import MVSNeRF, deterministic_choice, inference_precision, resolve_precision, train_gemm_choice
 from zest_utils import images_channels_last, volume_channels_last
 
 __all__ = ["rendering", "render_hierarchical", "raw2outputs", "raw2outputs_blending", "raw2alpha", "depth2dist",
@@ -115,8 +115,9 @@ def raw2outputs_blending(raw_dy, raw_rigid, raw_blend_w, z_vals, dists, raw_nois
 class _Views:
     """Volume + source images + cameras of one feature lookup, in kernel layout."""
 
-    def __init__(self, volume, imgs, cam_mat):
+    def __init__(self, volume, imgs, cam_mat, deterministic=False):
         self.vol_cl = self.imgs_cl = self.w2cs = self.intr = None
+        self.deterministic = bool(deterministic)    # the volume gradient of the lookups through the order-independent kernel
         if cam_mat is not None:
             self.w2cs = cam_mat['w2cs'][0].float().contiguous()
             self.intr = cam_mat['intrinsics'][0].float().contiguous()
@@ -242,12 +243,14 @@ def rendering(args, rays_pts, rays_ndc, depth_candidates, rays_dir,
                       "bf16 and evaluates in fp16", stacklevel=2)
 
     gemm = train_gemm_choice(args, train16) if train else zest_hip.GEMM_LIBRARY       # read once per call
+    det = deterministic_choice(args) if train else False                              # likewise
 
     shared = {}                 # per net: what its passes of this call share (packed weight streams, work buffer)
 
     def mlp(net, x, tc=None):
         if train:
-            return za.mlp_apply(net, x, tc, bf16=train16, shared=shared.setdefault(id(net), {}), gemm=gemm)
+            return za.mlp_apply(net, x, tc, bf16=train16, shared=shared.setdefault(id(net), {}), gemm=gemm,
+                                deterministic=det)
         p = net.nerf.engine_precision(mlp_prec)
         return zest_hip.mlp_fwd(net.desc(), p, net.packed(p, tc), x)
 
@@ -271,7 +274,7 @@ def rendering(args, rays_pts, rays_ndc, depth_candidates, rays_dir,
         return _draw_noise((1, R, S), ndc.device)[0] if raw_noise_std > 0 else None
 
     # ---- static NeRF (reference render_static, renderer.py:322-373)
-    vs = _Views(volume_feature_static, imgs, im_cam_mat)
+    vs = _Views(volume_feature_static, imgs, im_cam_mat, det)
     if train and rays_ndc.requires_grad:
         ndc = rays_ndc[0].float()
     x_s = encode(vs, volume_feature_static, ndc)
@@ -294,7 +297,7 @@ def rendering(args, rays_pts, rays_ndc, depth_candidates, rays_dir,
     # ---- dynamic NeRF (reference render_dynamic, renderer.py:378-575)
     net_d = _net(network_fn_dy, "network_fn_dy")
     _check_embedders(embedding_xyzt, embedding_dir, 4)
-    vd = _Views(volume_feature_dynamic, neighbour_frames, nb_cam_mat)
+    vd = _Views(volume_feature_dynamic, neighbour_frames, nb_cam_mat, det)
 
     def dyn_pass(ndc3, t):
         return mlp(net_d, encode(vd, volume_feature_dynamic, ndc3, float(t)))

@@ -90,14 +90,15 @@ def projection_from_ndc(w2c, H, W, f, weights_ref, raw_pts):
 
 
 # ---------------------------------------------------------------------------- plane sweep
-def homo_warp(src_feat, proj_mat, depth_values, src_grid=None, pad=0):
+def homo_warp(src_feat, proj_mat, depth_values, src_grid=None, pad=0, deterministic=False):
     """Warp a source feature map onto the fronto-parallel planes of the reference view
     (reference utils.py:49-99).  src_feat [1,C,H,W]; proj_mat [1,3,4] =
     src_proj @ ref_proj_inv; depth_values [1,D].  -> (warped [1,C,D,H+2pad,W+2pad],
     src_grid [1,D,W+2pad,H+2pad,2]: the reference's shape label for the normalised sampling
     positions, memory order [D][y][x]).  With src_grid given it is reused, as the reference does
     for the colour images.  Differentiable with respect to src_feat (HIP backward: scatter-add
-    through the bilinear taps); the sampling positions are data."""
+    through the bilinear taps); the sampling positions are data.  deterministic: that backward through the
+    order-independent kernel (zest_networks.deterministic_choice) instead of float atomics."""
     if src_feat.shape[0] != 1:
         raise RuntimeError("homo_warp: batch must be 1 (the reference never uses more)")
     if torch.is_grad_enabled() and proj_mat is not None and proj_mat.requires_grad:
@@ -110,7 +111,8 @@ def homo_warp(src_feat, proj_mat, depth_values, src_grid=None, pad=0):
         gin = src_grid.reshape(D, Hp, Wp, 2)
     if torch.is_grad_enabled() and src_feat.requires_grad:
         import zest_autograd
-        warped, grid = zest_autograd.HomoWarpFn.apply(src_feat[0], None if gin is not None else proj_mat[0], depth, gin, pad)
+        warped, grid = zest_autograd.HomoWarpFn.apply(src_feat[0], None if gin is not None else proj_mat[0], depth, gin, pad,
+                                                          bool(deterministic))
     elif gin is None:
         warped, grid = zest_hip.homo_warp(src_feat[0], proj_mat[0], depth, None, pad)
     else:

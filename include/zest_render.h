@@ -242,6 +242,39 @@ int zest_costreg_dgrad_launch_shape(int D, int H, int W, int *n_tiles, int *n_wg
 int zest_costreg_dgrad(const float *g, const float *w, int D, int H, int W, int cin, int cout, float *g_x,
                        void *stream);
 
+/* Gradients of the 2-D feature pyramid's convolutions (csrc/feature_grad.hip): Conv2d k x k, padding k / 2, no bias,
+ * (k, stride) = (3, 1) or (5, 2); the channel pairs of FeatureNet (3 x 3: cin <= 16 -> 8 or 16, 17 .. 32 -> 32; 5 x 5:
+ * cin <= 16 -> 16 or 32).  Ho = (Hi - 1) / stride + 1, Wo likewise; N Hi Wi 32 < 2^31.  The number contract of the two
+ * kernels above: operands rounded to bf16 (nearest even), fp32 accumulation, fp32 results, no atomics, partial sums
+ * added in a fixed order - the same bits on every call.
+ * zest_feature_wgrad: g_w[co][ci][ky][kx] = sum_{n,y,x} g[n,y,x,co] a[n, s y + ky - p, s x + kx - p, ci] (a = 0 outside),
+ *   g [N,Ho,Wo,cout]; a = leaky_relu(x pre[0] + pre[1], 0.01) in torch's two-rounding fp32 form with pre [2,cin], or x
+ *   itself where pre is NULL.  x is read through its element strides (sn, sy, sx, sc): channels-last raw outputs
+ *   (sc = 1) and the channel planes of an image alike.  Two launches: every workgroup writes one partial to `work`
+ *   (*work_bytes of the launch shape, 16-byte aligned), a finishing kernel adds them in order.  A unit is 32 output
+ *   pixels of one row (*n_units = N Ho ceil(Wo / 32)); workgroup w of *n_wg takes units [w upw, (w + 1) upw).
+ * zest_feature_dgrad: g_x[n,y,x,ci] = sum_{co,ky,kx} g[n,(y+p-ky)/s,(x+p-kx)/s,co] w[co][ci][ky][kx] over the taps whose
+ *   quotients are whole and inside the map; w the module's [cout,cin,k,k] fp32, cin 8, 16 or 32; g_x [N,Hi,Wi,cin]
+ *   channels-last, every element written exactly once.  Two launches: the weight is packed into `wpack` (*pack_bytes,
+ *   16-byte aligned), then the gather.  A tile is 32 positions of one row of g with all stride x stride parity classes
+ *   of input pixels over it (*n_tiles = N Ho ceil(Wo / 32)); wave v of workgroup w takes tiles 4 w + v + 4 *n_wg i.
+ * zest_feature_top_bwd: the 1 x 1 top layer (32 -> 32, bias), fp32 throughout: g_feats [N,32,h,w], raw [N,h,w,32],
+ *   pre [2,32], top_w [32,32] -> g_act [N,h,w,32] = g w, g_w [32,32] = g^T act(raw), g_b [32]; partial sums of *n_wg
+ *   workgroups (64 pixels a chunk, chunk c to workgroup c mod *n_wg) in `work` (*work_bytes), added in order.
+ * The launch-shape functions are host arithmetic only, the same code the launches run; result pointers may be NULL. */
+int zest_feature_wgrad_launch_shape(int N, int Hi, int Wi, int cin, int cout, int k, int stride, int *n_units,
+                                    int *units_per_wg, int *n_wg, size_t *work_bytes);
+int zest_feature_wgrad(const float *x, long long sn, long long sy, long long sx, long long sc, const float *pre,
+                       const float *g, int N, int Hi, int Wi, int cin, int cout, int k, int stride, void *work,
+                       float *g_w, void *stream);
+int zest_feature_dgrad_launch_shape(int N, int Hi, int Wi, int cin, int cout, int k, int stride, int *n_tiles,
+                                    int *n_wg, size_t *pack_bytes);
+int zest_feature_dgrad(const float *g, const float *w, int N, int Hi, int Wi, int cin, int cout, int k, int stride,
+                       void *wpack, float *g_x, void *stream);
+int zest_feature_top_bwd_launch_shape(int N, int h, int w, int *n_chunks, int *n_wg, size_t *work_bytes);
+int zest_feature_top_bwd(const float *g_feats, const float *raw, const float *pre, const float *top_w, int N, int h,
+                         int w, void *work, float *g_act, float *g_w, float *g_b, void *stream);
+
 /* Backward of the plane sweep (the MVSNet trains through it: reference train.py:270 optimises
  * generator.parameters(), networks.py:1077-1140 runs under autograd).  The trainable input is the
  * feature maps; images, homographies, depths and the in-frame counts carry no gradient.

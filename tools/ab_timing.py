@@ -1,6 +1,6 @@
 """The interleaved A/B timing protocol of the kernel benchmark tools (bench_sf_losses, bench_sf_step_loss,
 bench_sf_ray_terms, bench_patch_terms, bench_disc, bench_lpips, bench_image_metrics, bench_optimizer,
-bench_costreg_wgrad, bench_costreg_dgrad).  A tool keeps its inputs, its variants, the agreement check between them and
+bench_costreg_wgrad, bench_costreg_dgrad, bench_feature_grads).  A tool keeps its inputs, its variants, the agreement check between them and
 its result record; how they are timed is here, once:
 
   warm up      every variant, the baseline's second entry included: first launches load code objects and the libraries

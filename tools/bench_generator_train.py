@@ -1,7 +1,7 @@
 """One training-shaped step of the WHOLE generator (DyMVSNeRF_G.forward: both volume builders under autograd + ray sampling +
 train-mode rendering, then a loss and backward into the builders and both MLPs) at the NSFF geometry: where a real
 training step spends its time once the rendering path is 5.7 ms.
-    python tools/bench_generator_train.py [--precision 16] [--steps 5] [--deterministic]"""
+    python tools/bench_generator_train.py [--precision 16] [--steps 5] [--hip-wgrad] [--hip-dgrad] [--hip-feature-grads] [--deterministic]"""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -14,6 +14,7 @@ ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--library-costreg", action="store_true", help="MVSNet.zest_hip_costreg_train = False: the regularisation nets through the library under autograd (the product default in --precision 16 is their forward on the HIP kernels, zest_autograd.CostRegFn)")
 ap.add_argument("--hip-wgrad", action="store_true", help="MVSNet.zest_hip_costreg_wgrad = True: the weight gradient of each regularisation net's first layer from zest_costreg_wgrad (csrc/costreg_wgrad.hip) instead of the library (--precision 16 only)")
 ap.add_argument("--hip-dgrad", action="store_true", help="MVSNet.zest_hip_costreg_dgrad = True: the data gradient of each regularisation net's first layer from zest_costreg_dgrad (csrc/costreg_dgrad.hip) instead of the library (--precision 16 only)")
+ap.add_argument("--hip-feature-grads", action="store_true", help="MVSNet.zest_hip_feature_grads = True: the gradients of each feature pyramid's convolutions from csrc/feature_grad.hip instead of the library (--precision 16 only)")
 ap.add_argument("--deterministic", action="store_true", help="args.zest_deterministic = True: the volume, feature-map and bias gradients through the order-independent kernels (csrc/det_grads.hip) instead of float atomics")
 a = ap.parse_args()
 torch.backends.cudnn.benchmark = True
@@ -26,6 +27,8 @@ if a.hip_wgrad:
     args.zest_hip_costreg_wgrad = True
 if a.hip_dgrad:
     args.zest_hip_costreg_dgrad = True
+if a.hip_feature_grads:
+    args.zest_hip_feature_grads = True
 if a.deterministic:
     args.zest_deterministic = True
 

@@ -13,12 +13,15 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libzest_hip.so")
 SOURCES = ["capi.hip", "composite.hip", "composite_bwd.hip", "encode.hip", "rays.hip", "volume_cost.hip", "costreg.hip", "losses.hip", "sf_losses.hip", "sf_sample_losses.hip", "sf_ray_losses.hip", "patch_losses.hip", "disc.hip", "lpips.hip", "image_metrics.hip", "optim.hip", "mlp_plan.hip", "mlp.hip", "mlp_engine.hip", "mlp_train.hip", "train_gemm.hip", "mlp_train16.hip",
-           "mlp_train16_dw.hip", "fused.hip", "costreg_wgrad.hip", "costreg_dgrad.hip", "det_grads.hip"]
+           "mlp_train16_dw.hip", "fused.hip", "costreg_wgrad.hip", "costreg_dgrad.hip", "det_grads.hip", "feature_grad.hip"]
 # per-source flags.  The engine kernels outside the fused renderer (standalone MLP, training forward, backward data and
 # finishing kernels) are built without the SLP vectorizer for the reason given at VARIANTS below (training forward
 # -5 %, data kernel -3 %, finishing -2 %); the weight-gradient kernel, a translation unit of its own, keeps it: it runs
 # twice as long without (profiles/r03_ab_train_noslp.txt)
-SOURCE_FLAGS = {"mlp_engine.hip": ["-fno-slp-vectorize"], "mlp_train16.hip": ["-fno-slp-vectorize"]}
+SOURCE_FLAGS = {"mlp_engine.hip": ["-fno-slp-vectorize"], "mlp_train16.hip": ["-fno-slp-vectorize"],
+                # the pyramid's gradient kernels form act() = leaky_relu(raw scale + shift) with the two roundings of the torch
+                # expression they replace; a fused multiply-add there moves one bf16 operand in 10^5 to its other neighbour
+                "feature_grad.hip": ["-ffp-contract=off"]}
 # fused renderer instantiations: fused_variant.hip once per (operand type, feature shape);
 # heaviest first so the pool drains evenly
 _SHAPES = [("s4d2", 4, "true", 2, "false"), ("s2d2", 2, "true", 2, "false"), ("s4d0", 4, "true", 0, "false"),

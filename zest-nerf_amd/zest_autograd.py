@@ -696,17 +696,47 @@ def costreg_apply(net, cost_vol, passes, hip_wgrad=False, hip_dgrad=False):
 class FeatureFn(Function):
     """FeatureNet under autograd with its forward on the HIP kernels (csrc/costreg.hip, zest_conv2d_fwd), as CostRegFn:
     norm + activation backward in HIP (zest_costreg_bn_bwd), convolution backward through aten.convolution_backward on
-    the kept raw outputs, the 1x1 top layer as matrix products.  Inputs after `passes`: the eight convolution weights,
-    the top layer's weight and bias, then (weight, bias) of the eight norms."""
+    the kept raw outputs, the 1x1 top layer as matrix products.
+    hip_grads (MVSNet.zest_hip_feature_grads; opt-in, holds for bf16 operands - passes == 1 - only: with passes == 3 it
+    changes nothing): the convolutions' gradients come from csrc/feature_grad.hip instead.  zest_hip.feature_top_bwd runs
+    first, then per layer from 7 to 0 zest_costreg_bn_bwd, zest_hip.feature_wgrad on the kept raw output and norm
+    constants of the layer below (the kernel forms the activation itself; layer 0 reads the kept image) and, except for
+    layer 0, zest_hip.feature_dgrad, whose channels-last fp32 result is what the next norm backward reads: no library
+    convolution, no cast, no layout copy, no float atomic, and fp32 results that are not rounded to bf16.  Nothing extra
+    is kept between forward and backward.
+    Inputs after `hip_grads`: the eight convolution weights, the top layer's weight and bias, then (weight, bias) of the
+    eight norms."""
 
     @staticmethod
-    def forward(ctx, imgs, net, passes, *params):
+    def forward(ctx, imgs, net, passes, hip_grads, *params):
         feats, raw, pr, mo = net.forward_hip(imgs, passes, keep=True)
+        ctx.hip_grads = bool(hip_grads) and passes == 1
         _keep_layers(ctx, net, passes, imgs, raw, pr, mo, params)
         return feats.permute(0, 3, 1, 2)
 
     @staticmethod
+    def _backward_hip(ctx, g_feats):
+        imgs, raw, pr, mo, params, _ = _kept_layers(ctx)
+        n = ctx.n
+        W, top_w, gam = params[:n], params[n], params[n + 2::2]
+        layers = ctx.net.hip_layers()
+        g_a, g_top_w, g_top_b = zest_hip.feature_top_bwd(g_feats.float().contiguous(), raw[n - 1], pr[n - 1], top_w)
+        gW, gG, gB = [None] * n, [None] * n, [None] * n
+        for i in range(n - 1, -1, -1):
+            g_r, gG[i], gB[i] = _norm_bwd(i, g_a, raw, pr, mo, gam)
+            conv = layers[i].conv
+            k, stride = conv.kernel_size[0], conv.stride[0]
+            if i > 0:
+                gW[i] = zest_hip.feature_wgrad(raw[i - 1], pr[i - 1], g_r, k, stride, conv.in_channels)
+                g_a = zest_hip.feature_dgrad(g_r, W[i], stride, raw[i - 1].shape[1:3])
+            else:
+                gW[i] = zest_hip.feature_wgrad(imgs, None, g_r, k, stride, conv.in_channels)
+        return (None, None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
+
+    @staticmethod
     def backward(ctx, g_feats):
+        if ctx.hip_grads:
+            return FeatureFn._backward_hip(ctx, g_feats)
         imgs, raw, pr, mo, params, _ = _kept_layers(ctx)
         n, low = ctx.n, ctx.low
         W, top_w, gam = params[:n], params[n], params[n + 2::2]
@@ -725,12 +755,16 @@ class FeatureFn(Function):
                                    conv.kernel_size[0] // 2, False, [i > 0, True, False])
             if i > 0:
                 g_a = g_x.permute(0, 2, 3, 1)
-        return (None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
+        return (None, None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
 
 
-def feature_apply(net, imgs, passes):
-    """FeatureNet(imgs [N,3,H,W]) -> [N,32,H/4,W/4] through FeatureFn."""
+def feature_apply(net, imgs, passes, hip_grads=False):
+    """FeatureNet(imgs [N,3,H,W]) -> [N,32,H/4,W/4] through FeatureFn.  hip_grads: the convolutions' gradients from the
+    HIP kernels of csrc/feature_grad.hip, see there (opt-in; passes == 1 only - with passes == 3 it changes nothing)."""
     layers = net.hip_layers()
     params = ([m.conv.weight for m in layers] + [net.toplayer.weight, net.toplayer.bias]
               + [p for m in layers for p in (m.bn.weight, m.bn.bias)])
-    return FeatureFn.apply(imgs.float(), net, passes, *params)
+    imgs = imgs.float()
+    if hip_grads:
+        imgs = imgs.contiguous()              # zest_hip.feature_wgrad reads the kept image through fixed strides
+    return FeatureFn.apply(imgs, net, passes, bool(hip_grads), *params)

@@ -130,6 +130,12 @@ _SIGS = {
     "zest_costreg_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_costreg_dgrad_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "zest_costreg_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zest_feature_wgrad_launch_shape": (_i, [_i] * 7 + [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
+    "zest_feature_wgrad": (_i, [_vp] + [C.c_longlong] * 4 + [_vp, _vp] + [_i] * 7 + [_vp, _vp, _vp]),
+    "zest_feature_dgrad_launch_shape": (_i, [_i] * 7 + [C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
+    "zest_feature_dgrad": (_i, [_vp, _vp] + [_i] * 7 + [_vp, _vp, _vp]),
+    "zest_feature_top_bwd_launch_shape": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
+    "zest_feature_top_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "zest_volume_cost_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_homo_warp_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "zest_volume_cost_bwd_det_work_bytes": (_sz, [_i, _i, _i]),
@@ -1294,6 +1300,121 @@ def costreg_dgrad(g_cl, weight, out=None):
     _check(lib().zest_costreg_dgrad(_ptr(g_cl), _ptr(weight), D, H, W, cin, 8, _ptr(out), _stream(g_cl)),
            "zest_costreg_dgrad")
     return out
+
+
+# ------------------------------------------------------------------ gradients of the feature pyramid (csrc/feature_grad.hip)
+def _feature_operand(who, name, t, what, ok, device=None):
+    """One operand of the pyramid's gradient kernels: a contiguous fp32 tensor of the stated layout on a HIP device
+    (`device`: the one an earlier operand is on).  dtype, layout and shape first: the C ABI sees pointers and sizes only."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
+        raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
+                           % (who, name, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
+                              if torch.is_tensor(t) else type(t).__name__))
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (all tensors on one)" % (who, name, t.device))
+    return t.device
+
+
+def _conv_out(n, stride):
+    return (n - 1) // stride + 1
+
+
+def feature_wgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride):
+    """-> (units, units per workgroup, workgroups, fp32 elements of the partial-sum buffer) of feature_wgrad (a unit: 32
+    output pixels of one row; workgroup w takes units [w upw, (w + 1) upw)).  Host arithmetic, the code the launch runs."""
+    units, upw, wgs, nbytes = _i(0), _i(0), _i(0), _sz(0)
+    _check(lib().zest_feature_wgrad_launch_shape(int(N), int(Hi), int(Wi), int(cin), int(cout), int(k), int(stride), C.byref(units),
+                                                 C.byref(upw), C.byref(wgs), C.byref(nbytes)), "zest_feature_wgrad_launch_shape")
+    return units.value, upw.value, wgs.value, nbytes.value // 4
+
+
+def feature_wgrad(x, pre, g, k, stride, cin):
+    """Weight gradient of one Conv2d of the feature pyramid (k x k, padding k // 2, no bias; (k, stride) = (3, 1) or
+    (5, 2)) -> g_w [cout,cin,k,k] fp32.  g [N,Ho,Wo,cout]: costreg_bn_bwd's channels-last result.  With pre [2,cin]: x
+    [N,Hi,Wi,cin] is the previous layer's raw channels-last output and the kernel forms leaky_relu(x pre[0] + pre[1])
+    itself; with pre None: x [N,cin,Hi,Wi] is the layer's input as it is (the image, channel planes).  bf16-rounded
+    operands, fp32 accumulation, fp32 result, no atomics: the same bits on every call."""
+    who, cin, k, stride = "zest_hip.feature_wgrad", int(cin), int(k), int(stride)
+    if pre is None:
+        dev = _feature_operand(who, "x", x, "[N,%d,Hi,Wi] (pre is None: the layer's own input)" % cin,
+                               lambda t: t.dim() == 4 and t.shape[1] == cin)
+        N, _, Hi, Wi = x.shape
+        strides = (cin * Hi * Wi, Wi, 1, Hi * Wi)
+    else:
+        dev = _feature_operand(who, "x", x, "[N,Hi,Wi,%d]" % cin, lambda t: t.dim() == 4 and t.shape[3] == cin)
+        N, Hi, Wi, _ = x.shape
+        strides = (Hi * Wi * cin, Wi * cin, cin, 1)
+        _feature_operand(who, "pre", pre, "[2,%d]" % cin, lambda t: tuple(t.shape) == (2, cin), dev)
+    if stride < 1:
+        raise RuntimeError("%s: stride %d" % (who, stride))
+    Ho, Wo = _conv_out(Hi, stride), _conv_out(Wi, stride)
+    _feature_operand(who, "g", g, "[%d,%d,%d,cout]" % (N, Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[:3]) == (N, Ho, Wo), dev)
+    cout = int(g.shape[3])
+    need = feature_wgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride)[3]      # refuses a layer shape without a kernel
+    work = torch.empty(need, device=dev, dtype=torch.float32)
+    out = torch.empty(cout, cin, k, k, device=dev, dtype=torch.float32)
+    _check(lib().zest_feature_wgrad(_ptr(x), *strides, _ptr(pre), _ptr(g), N, Hi, Wi, cin, cout, k, stride, _ptr(work), _ptr(out),
+                                    _stream(g)), "zest_feature_wgrad")
+    return out
+
+
+def feature_dgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride):
+    """-> (tiles, workgroups, bytes of the packed weight) of feature_dgrad (a tile: 32 positions of one row of g with all
+    stride x stride parity classes of input pixels over it; wave v of workgroup w takes tiles 4 w + v + 4 workgroups i).
+    Host arithmetic, the code the launch runs."""
+    tiles, wgs, nbytes = _i(0), _i(0), _sz(0)
+    _check(lib().zest_feature_dgrad_launch_shape(int(N), int(Hi), int(Wi), int(cin), int(cout), int(k), int(stride), C.byref(tiles),
+                                                 C.byref(wgs), C.byref(nbytes)), "zest_feature_dgrad_launch_shape")
+    return tiles.value, wgs.value, nbytes.value
+
+
+def feature_dgrad(g, w, stride, in_hw):
+    """Data gradient of one Conv2d of the feature pyramid: g [N,Ho,Wo,cout] (costreg_bn_bwd's channels-last result), w the
+    module's [cout,cin,k,k] fp32 weight, in_hw = (Hi, Wi) the extents of the layer's input -> g_x [N,Hi,Wi,cin]
+    channels-last fp32, what the next costreg_bn_bwd reads.  A gather per parity class of the input pixel: every element
+    written once, bf16-rounded operands, fp32 accumulation, fp32 result, no atomics."""
+    who, stride = "zest_hip.feature_dgrad", int(stride)
+    Hi, Wi = (int(v) for v in in_hw)
+    if stride < 1 or Hi < 1 or Wi < 1:
+        raise RuntimeError("%s: stride %d, input extents %d x %d" % (who, stride, Hi, Wi))
+    Ho, Wo = _conv_out(Hi, stride), _conv_out(Wi, stride)
+    dev = _feature_operand(who, "g", g, "[N,%d,%d,cout]" % (Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[1:3]) == (Ho, Wo))
+    N, cout = int(g.shape[0]), int(g.shape[3])
+    _feature_operand(who, "w", w, "[%d,cin,k,k]" % cout, lambda t: t.dim() == 4 and t.shape[0] == cout and t.shape[2] == t.shape[3], dev)
+    cin, k = int(w.shape[1]), int(w.shape[2])
+    nbytes = feature_dgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride)[2]    # refuses a layer shape without a kernel
+    wpack = torch.empty(nbytes // 2, device=dev, dtype=torch.int16)
+    out = torch.empty(N, Hi, Wi, cin, device=dev, dtype=torch.float32)
+    _check(lib().zest_feature_dgrad(_ptr(g), _ptr(w), N, Hi, Wi, cin, cout, k, stride, _ptr(wpack), _ptr(out), _stream(g)),
+           "zest_feature_dgrad")
+    return out
+
+
+def feature_top_bwd_launch_shape(N, h, w):
+    """-> (chunks of 64 pixels, workgroups, fp32 elements of the partial-sum buffer) of feature_top_bwd (chunk c goes to
+    workgroup c mod workgroups).  Host arithmetic, the code the launch runs."""
+    chunks, wgs, nbytes = _i(0), _i(0), _sz(0)
+    _check(lib().zest_feature_top_bwd_launch_shape(int(N), int(h), int(w), C.byref(chunks), C.byref(wgs), C.byref(nbytes)),
+           "zest_feature_top_bwd_launch_shape")
+    return chunks.value, wgs.value, nbytes.value // 4
+
+
+def feature_top_bwd(g_feats, raw, pre, top_w):
+    """Backward of the pyramid's 1 x 1 top layer (32 -> 32 with bias), fp32 throughout: g_feats [N,32,h,w], raw [N,h,w,32]
+    and pre [2,32] of the last 3 x 3 layer, top_w [32,32,1,1] -> (g_act [N,h,w,32] channels-last, g_top_w like top_w,
+    g_top_b [32]).  The two sums over pixels are added in a fixed order: the same bits on every call."""
+    who = "zest_hip.feature_top_bwd"
+    dev = _feature_operand(who, "g_feats", g_feats, "[N,32,h,w]", lambda t: t.dim() == 4 and t.shape[1] == 32)
+    N, _, h, w = g_feats.shape
+    _feature_operand(who, "raw", raw, "[%d,%d,%d,32]" % (N, h, w), lambda t: tuple(t.shape) == (N, h, w, 32), dev)
+    _feature_operand(who, "pre", pre, "[2,32]", lambda t: tuple(t.shape) == (2, 32), dev)
+    _feature_operand(who, "top_w", top_w, "[32,32,1,1]", lambda t: tuple(t.shape) in ((32, 32, 1, 1), (32, 32)), dev)
+    work = torch.empty(feature_top_bwd_launch_shape(N, h, w)[2], device=dev, dtype=torch.float32)
+    g_act = torch.empty(N, h, w, 32, device=dev, dtype=torch.float32)
+    g_w, g_b = torch.empty_like(top_w), torch.empty(32, device=dev, dtype=torch.float32)
+    _check(lib().zest_feature_top_bwd(_ptr(g_feats), _ptr(raw), _ptr(pre), _ptr(top_w), N, h, w, _ptr(work), _ptr(g_act), _ptr(g_w),
+                                      _ptr(g_b), _stream(g_feats)), "zest_feature_top_bwd")
+    return g_act, g_w, g_b
 
 
 def costreg_out(raw_a, pre_a, raw_b, pre_b):

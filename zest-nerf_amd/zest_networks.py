@@ -696,6 +696,10 @@ class MVSNet(nn.Module):
         # opt-in, likewise: the data gradient of cost_reg_2.conv0 - the gradient towards the cost volume - from the HIP
         # kernel, as fp32 channel planes (nothing extra is kept for it).  No effect in fp32 mode.
         self.zest_hip_costreg_dgrad = False
+        # opt-in, likewise: the gradients of the feature pyramid's convolutions - weight, data and the 1 x 1 top layer -
+        # from the HIP kernels of csrc/feature_grad.hip (zest_autograd.FeatureFn; nothing extra is kept).  No effect in
+        # fp32 mode.
+        self.zest_hip_feature_grads = False
         # opt-in (args.zest_deterministic / ZEST_DETERMINISTIC=1, see deterministic_choice): the gradient towards the
         # feature maps through the order-independent plane-sweep backward instead of float atomics
         self.zest_deterministic = False
@@ -753,7 +757,9 @@ class MVSNet(nn.Module):
         elif (hip_train and B == 1 and self.feature.hip_supported() and self.feature.toplayer.bias is not None
               and all(m.training for m in self.feature.modules() if isinstance(m, ActivatedBatchNorm))):
             import zest_autograd                      # the pyramid's forward on the HIP kernels under autograd (FeatureFn)
-            feats = zest_autograd.feature_apply(self.feature, imgs[0], passes)[None]
+            # zest_hip_feature_grads (opt-in, --precision 16 only): the convolutions' gradients in HIP as well
+            feats = zest_autograd.feature_apply(self.feature, imgs[0], passes,
+                                                hip_grads=bool(getattr(self, "zest_hip_feature_grads", False)))[None]
         else:
             feats, _ = self.feature(imgs.reshape(B * V, 3, H, W))
             feats = feats.view(B, V, *feats.shape[1:])
@@ -826,7 +832,8 @@ class _Generator(nn.Module):
             if (not train and getattr(self.args, "zest_graph_builders", True) and isinstance(net, MVSNet)
                     and net.feature.hip_supported() and net.hip_path(imgs, self.args.pad)):
                 return self._volume_replayed(net, imgs, proj_mats, near_far)
-            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad", "zest_deterministic"):
+            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad", "zest_hip_feature_grads",
+                         "zest_deterministic"):
                 if train and isinstance(net, MVSNet) and getattr(self.args, name, None) is not None:
                     setattr(net, name, bool(getattr(self.args, name)))      # the caller's choice, else MVSNet's default
             if train and isinstance(net, MVSNet) and os.environ.get("ZEST_DETERMINISTIC", ""):

@@ -2,7 +2,7 @@
 zest_autograd.FeatureFn with hip_grads).  Plain torch on the CPU: this file calls no project kernel; the judges,
 references and preconditions are those of builder_grad_cases.py.
 
-The walk with the switch on (zest_autograd.FeatureFn._backward_hip): zest_hip.feature_top_bwd in fp32; then per layer
+The walk with the switch on (zest_autograd.FeatureFn.backward over _feature_hip_grads): zest_hip.feature_top_bwd in fp32; then per layer
 from 7 to 0 zest_costreg_bn_bwd, zest_hip.feature_wgrad on the kept raw output and norm constants of the layer below (the
 kernel forms act() itself; layer 0 reads the image) and, except for layer 0, zest_hip.feature_dgrad.  Number contract of
 the two convolution kernels: operands rounded to bf16 (nearest even), fp32 sums, fp32 results that are NOT rounded.  So

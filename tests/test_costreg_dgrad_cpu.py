@@ -1,7 +1,6 @@
 """CPU: the judge of the first layer's data-gradient kernel (tests/dgrad_cases.py) against autograd, what it rejects,
 the host-only launch plan of csrc/costreg_dgrad.hip, every refusal of the C ABI and of the binding, and the way the
 switch reaches CostRegNet (no GPU)."""
-import argparse
 import ctypes as C
 import random
 
@@ -143,32 +142,12 @@ def test_binding_refusals():
             zh.costreg_dgrad(g, torch.zeros(8, cin, 3, 3, 3))
 
 
-def test_switch_reaches_the_net_through_the_builder_and_the_generator():
-    """args.zest_hip_costreg_dgrad -> MVSNet.zest_hip_costreg_dgrad in _Generator._volume, as zest_hip_costreg_wgrad;
-    the attributes are False by default, an absent or None argument leaves the builder's alone, and so does a pass
-    without autograd."""
+def test_switch_is_no_field_of_the_regularisation_net():
+    """The switch is an argument of costreg_apply, not a field of the regularisation net (the way from MVSNet.forward to
+    costreg_apply needs a device: tests/test_hip_costreg_dgrad.py; the way to MVSNet: tests/test_builder_switches_cpu.py)."""
     import zest_networks as networks
-
-    class Net(networks.MVSNet):
-        def forward(self, imgs, proj_mats, near_far, pad=0, **kw):
-            return (torch.zeros(1, 8, 2, 2, 2) + self.cost_reg_2.conv0.conv.weight.sum() * 0,)
-
-    net = Net()
-    assert net.zest_hip_costreg_dgrad is False and networks.MVSNet().zest_hip_costreg_dgrad is False
-    # the switch is an argument of costreg_apply, not a field of the regularisation net (the way from MVSNet.forward to
-    # costreg_apply needs a device: tests/test_hip_costreg_dgrad.py)
+    net = networks.MVSNet()
     assert not hasattr(networks.CostRegNet(41), "zest_hip_dgrad") and not hasattr(net.cost_reg_2, "zest_hip_dgrad")
-    gen = networks._Generator()
-    imgs = torch.zeros(1, 3, 3, 8, 8)
-    for given, want in (((), False), ((None,), False), ((True,), True), ((None,), True), ((0,), False), ((1,), True)):
-        gen.args = argparse.Namespace(precision=32, pad=0, **({"zest_hip_costreg_dgrad": given[0]} if given else {}))
-        gen._volume(net, imgs, None, None)
-        assert net.zest_hip_costreg_dgrad is want, given
-        assert net.zest_hip_costreg_wgrad is False       # the other switch is not touched
-    with torch.no_grad():                                # no training pass: the builder keeps its setting
-        gen.args = argparse.Namespace(precision=32, pad=0, zest_hip_costreg_dgrad=False, zest_graph_builders=False)
-        gen._volume(net, imgs, None, None)
-    assert net.zest_hip_costreg_dgrad is True
 
 
 def test_costreg_apply_keeps_its_signature():

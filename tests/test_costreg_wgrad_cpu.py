@@ -1,7 +1,6 @@
 """CPU: the judge of the first layer's weight-gradient kernel (tests/wgrad_cases.py) against autograd, what it rejects,
 the host-only launch plan of csrc/costreg_wgrad.hip, every refusal of the C ABI and of the binding, and the way the
 switch reaches MVSNet (no GPU)."""
-import argparse
 import ctypes as C
 import random
 
@@ -135,29 +134,6 @@ def test_binding_refusals():
     for cin in (0, 49, -3):
         with pytest.raises(RuntimeError, match="cin %d, expected 1 .. 48" % cin):
             zh.costreg_wgrad(x, g, cin)
-
-
-def test_switch_reaches_the_builder_through_the_generator():
-    """args.zest_hip_costreg_wgrad -> MVSNet.zest_hip_costreg_wgrad in _Generator._volume, as zest_hip_costreg_train;
-    the attribute is False by default and an absent or None argument leaves it alone."""
-    import zest_networks as networks
-
-    class Net(networks.MVSNet):
-        def forward(self, imgs, proj_mats, near_far, pad=0, **kw):
-            return (torch.zeros(1, 8, 2, 2, 2) + self.cost_reg_2.conv0.conv.weight.sum() * 0,)
-
-    net = Net()
-    assert net.zest_hip_costreg_wgrad is False and networks.MVSNet().zest_hip_costreg_wgrad is False
-    gen = networks._Generator()
-    imgs = torch.zeros(1, 3, 3, 8, 8)
-    for given, want in (((), False), ((None,), False), ((True,), True), ((None,), True), ((0,), False), ((1,), True)):
-        gen.args = argparse.Namespace(precision=32, pad=0, **({"zest_hip_costreg_wgrad": given[0]} if given else {}))
-        gen._volume(net, imgs, None, None)
-        assert net.zest_hip_costreg_wgrad is want, given
-    with torch.no_grad():                                # no training pass: the builder keeps its setting
-        gen.args = argparse.Namespace(precision=32, pad=0, zest_hip_costreg_wgrad=False, zest_graph_builders=False)
-        gen._volume(net, imgs, None, None)
-    assert net.zest_hip_costreg_wgrad is True
 
 
 def test_costreg_apply_takes_the_switch_and_defaults_to_off():

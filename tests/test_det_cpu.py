@@ -34,8 +34,8 @@ def test_switch_defaults_to_off_and_the_environment_overrides_the_argument(monke
 
 
 def test_switch_reaches_the_builder_through_the_generator(monkeypatch):
-    """args.zest_deterministic -> MVSNet.zest_deterministic in _Generator._volume, as zest_hip_costreg_wgrad: the
-    attribute is False by default and an absent or None argument leaves it alone; the environment overrides both."""
+    """args.zest_deterministic -> MVSNet.zest_deterministic in _Generator._volume as every switch of the builder
+    (tests/test_builder_switches_cpu.py); here: the environment overrides both the argument and its absence."""
     import zest_networks as networks
     monkeypatch.delenv("ZEST_DETERMINISTIC", raising=False)
 
@@ -44,16 +44,10 @@ def test_switch_reaches_the_builder_through_the_generator(monkeypatch):
             return (torch.zeros(1, 8, 2, 2, 2) + self.cost_reg_2.conv0.conv.weight.sum() * 0,)
 
     net = Net()
-    assert net.zest_deterministic is False and networks.MVSNet().zest_deterministic is False
     gen = networks._Generator()
     imgs = torch.zeros(1, 3, 3, 8, 8)
-    for given, want in (((), False), ((None,), False), ((True,), True), ((None,), True), ((0,), False), ((1,), True)):
-        gen.args = argparse.Namespace(precision=32, pad=0, **({"zest_deterministic": given[0]} if given else {}))
-        gen._volume(net, imgs, None, None)
-        assert net.zest_deterministic is want, given
-    with torch.no_grad():                                # no training pass: the builder keeps its setting
-        gen.args = argparse.Namespace(precision=32, pad=0, zest_deterministic=False, zest_graph_builders=False)
-        gen._volume(net, imgs, None, None)
+    gen.args = argparse.Namespace(precision=32, pad=0, zest_deterministic=True)
+    gen._volume(net, imgs, None, None)
     assert net.zest_deterministic is True
     monkeypatch.setenv("ZEST_DETERMINISTIC", "0")
     gen.args = argparse.Namespace(precision=32, pad=0, zest_deterministic=True)

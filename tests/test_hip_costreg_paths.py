@@ -412,6 +412,26 @@ def test_bn_bwd_against_float64_autograd(hip, C, big):
     assert all(torch.equal(a, b) for a, b in zip(again, (g_raw, g_gamma, g_beta)))
 
 
+def test_norm_constants_of_another_layer_are_refused_before_any_launch(hip, monkeypatch):
+    """The kernels read pre and moments as [2,C] and gamma as [C] fp32 at the pointers they are given: constants of a
+    16-channel layer, of another number format or on another device handed to an 8-channel layer are refused by the
+    binding, before it calls into the library at all."""
+    import zest_hip
+    raw, g_act = torch.randn(2, 2, 4, 8, device=DEV), torch.randn(2, 2, 4, 8, device=DEV)
+    pre, moments, gamma = torch.ones(2, 8, device=DEV), torch.ones(2, 8, device=DEV), torch.ones(8, device=DEV)
+    monkeypatch.setattr(zest_hip, "lib", lambda: pytest.fail("the refusal must come before the first call into the library"))
+    for args, text in (((torch.ones(2, 16, device=DEV), moments, gamma), "pre must be a contiguous fp32 tensor"),
+                       ((pre, moments.double(), gamma), "moments must be a contiguous fp32 tensor"),
+                       ((pre, moments, torch.ones(16, device=DEV)), "gamma must be a contiguous fp32 tensor"),
+                       ((pre, moments.cpu(), gamma), "moments is on cpu")):
+        with pytest.raises(RuntimeError, match="zest_hip.costreg_bn_bwd: " + text):
+            zest_hip.costreg_bn_bwd(raw, g_act, *args)
+    for args, text in (((pre.cpu(), pre), "pre_a is on cpu"), ((pre, pre.cpu()), "pre_b is on cpu"),
+                       ((torch.ones(2, 16, device=DEV), pre), "pre_a must be"), ((pre, pre.double()), "pre_b must be")):
+        with pytest.raises(RuntimeError, match="zest_hip.costreg_out: " + text):
+            zest_hip.costreg_out(raw, args[0], g_act, args[1])
+
+
 # ------------------------------------------------------------------------------------------------ g: the nets at full size
 def _randomise_norms(net):
     import zest_networks as networks

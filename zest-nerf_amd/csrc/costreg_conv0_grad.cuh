@@ -1,13 +1,11 @@
-// What the two gradient kernels of CostRegNet.conv0 share (costreg_wgrad.hip, costreg_dgrad.hip): the layer's shape,
-// the bf16 rounding of one value and the refusals both entry points make before a launch.
+// What the two gradient kernels of CostRegNet.conv0 share (costreg_wgrad.hip, costreg_dgrad.hip): the layer's shape
+// and the refusals both entry points make before a launch.
 #pragma once
 #include "mlp_engine.cuh"
 
 namespace zest {
 
 constexpr int kCO = 8, kCI = 48, kTaps = 27;     // output channels, padded input channels, 3 x 3 x 3 taps
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)(pack_bf16(v, 0.f) & 0xFFFFu); }
 
 // The refusals of zest_costreg_wgrad / zest_costreg_dgrad, in the order both make them; `who` is the entry point's
 // name, `operands` names the pointers that must be 16-byte aligned.  extents_ok: the file's own check of D, H, W.

@@ -122,6 +122,28 @@ inline int ceil_log2(long long n) {                // smallest k with n <= 2^k, 
 inline size_t fixed_work_bytes(long long n) { return kFixedHeaderBytes + (size_t)n * sizeof(unsigned long long); }
 inline int absmax_grid(long long n) { return (int)std::min<long long>((n + kThreads - 1) / kThreads, 2048); }
 
+struct AbsMax { const float *p; long long n, cols, ld; };     // one pre-pass: absmax_kernel's p, n, cols, ld
+
+// Steps 1 - 4 of a scatter-add (above), once: pre-pass i leaves its maximum in header slot i, scatter(hdr, acc, n_log2) launches
+// the family's kernel on the n_c contributions (with none: neither runs), and the finishing launch writes all n elements of out.
+template <class Scatter>
+void fixed_scatter(void *work, long long n_c, long long n, std::initializer_list<AbsMax> maxima, double c, float *out,
+                   hipStream_t st, Scatter scatter) {
+    FixedHeader *hdr = (FixedHeader *)work;
+    unsigned long long *acc = (unsigned long long *)((char *)work + kFixedHeaderBytes);
+    (void)hipMemsetAsync(work, 0, fixed_work_bytes(n), st);
+    const int n_log2 = ceil_log2(std::max(n_c, 1ll));
+    if (n_c > 0) {
+        int slot = 0;
+        for (const AbsMax &m : maxima)
+            hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(m.n)), dim3(kThreads), 0, st, m.p, m.n, m.cols, m.ld,
+                               &hdr->max_bits[slot++]);
+        scatter(hdr, acc, n_log2);
+    }
+    hipLaunchKernelGGL(fixed_finish_kernel, dim3(zest_div_up(n, kThreads)), dim3(kThreads), 0, st, hdr, (int)maxima.size(), c,
+                       n_log2, acc, n, out);
+}
+
 }  // namespace
 
 namespace zest {
@@ -193,19 +215,11 @@ extern "C" int zest_encode_bwd_det(const float *g_x, const float *ndc, int R, in
     const long long M = (long long)R * S, n_c = M * 8, n = (long long)D * Hv * Wv * 8;
     ZEST_CHECK_ARG(n_c <= kMaxContributions, "zest_encode_bwd_det: %lld contributions (R S 8) exceed 2^32: split the batch", n_c);
     hipStream_t st = (hipStream_t)stream;
-    FixedHeader *hdr = (FixedHeader *)work;
-    unsigned long long *acc = (unsigned long long *)((char *)work + kFixedHeaderBytes);
-    (void)hipMemsetAsync(work, 0, fixed_work_bytes(n), st);
-    const int n_log2 = ceil_log2(std::max(n_c, 1ll));
-    if (R > 0) {
-        const int c_in = (3 + (has_time ? 1 : 0)) * 21 + 8 + 4 * V + 27, P = (3 + (has_time ? 1 : 0)) * 21;
-        hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n_c)), dim3(kThreads), 0, st, g_x + P, n_c, 8ll, (long long)c_in,
-                           &hdr->max_bits[0]);
+    const int c_in = (3 + (has_time ? 1 : 0)) * 21 + 8 + 4 * V + 27, P = (3 + (has_time ? 1 : 0)) * 21;
+    fixed_scatter(work, n_c, n, {{g_x + P, n_c, 8ll, (long long)c_in}}, 1.0, g_vol_cl, st, [&](auto *hdr, auto *acc, int n_log2) {
         hipLaunchKernelGGL(encode_bwd_det_kernel, dim3(zest_div_up(n_c, kThreads)), dim3(kThreads), 0, st, g_x, ndc, R, S,
                            has_time ? 1 : 0, (const float4 *)vol_cl, D, Hv, Wv, V, g_ndc, g_vol_cl, hdr, acc, n_log2);
-    }
-    hipLaunchKernelGGL(fixed_finish_kernel, dim3(zest_div_up(n, kThreads)), dim3(kThreads), 0, st, hdr, 1, 1.0, n_log2, acc,
-                       n, g_vol_cl);
+    });
     ZEST_RETURN_LAUNCH("zest_encode_bwd_det");
 }
 
@@ -218,27 +232,17 @@ extern "C" int zest_volume_cost_bwd_det(const float *feats_cl, const float *proj
     ZEST_CHECK_ARG(aligned16(work), "zest_volume_cost_bwd_det: work must be 16-byte aligned");
     const long long nvox = (long long)D * (H + 2 * pad) * (W + 2 * pad);
     ZEST_CHECK_ARG(nvox < (1ll << 31), "zest_volume_cost_bwd_det: %lld voxels exceed the 32-bit index range", nvox);
-    const long long n_c = nvox * V * 4, n = (long long)V * H * W * kC;
+    const long long n_c = nvox * V * 4, n = (long long)V * H * W * kC, ng = nvox * kC;
     ZEST_CHECK_ARG(n_c <= kMaxContributions,
                    "zest_volume_cost_bwd_det: %lld contributions (voxels x views x 4 taps) exceed 2^32", n_c);
     hipStream_t st = (hipStream_t)stream;
-    FixedHeader *hdr = (FixedHeader *)work;
-    unsigned long long *acc = (unsigned long long *)((char *)work + kFixedHeaderBytes);
-    (void)hipMemsetAsync(work, 0, fixed_work_bytes(n), st);
-    const int n_log2 = ceil_log2(n_c);
-    const long long ng = nvox * kC;
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ng)), dim3(kThreads), 0, st, g_img_feat + (size_t)(3 * V) * nvox, ng,
-                       ng, ng, &hdr->max_bits[0]);
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n)), dim3(kThreads), 0, st, feats_cl, n, n, n, &hdr->max_bits[1]);
-#define ZEST_SWEEP(VT)                                                                                       \
-    hipLaunchKernelGGL(volume_cost_bwd_det_kernel<VT>, dim3(zest_div_up(nvox, 64)), dim3(64), 0, st, feats_cl, proj, \
-                       depth, V, D, H, W, pad, g_img_feat, g_feats_cl, hdr, acc, n_log2)
-    if (V == 3) ZEST_SWEEP(3);
-    else if (V == 4) ZEST_SWEEP(4);
-    else ZEST_SWEEP(0);
-#undef ZEST_SWEEP
-    hipLaunchKernelGGL(fixed_finish_kernel, dim3(zest_div_up(n, kThreads)), dim3(kThreads), 0, st, hdr, 2, kSweepFactor,
-                       n_log2, acc, n, g_feats_cl);
+    auto sweep = volume_cost_bwd_det_kernel<3>;
+    if (V != 3) sweep = V == 4 ? volume_cost_bwd_det_kernel<4> : volume_cost_bwd_det_kernel<0>;
+    fixed_scatter(work, n_c, n, {{g_img_feat + (size_t)(3 * V) * nvox, ng, ng, ng}, {feats_cl, n, n, n}}, kSweepFactor, g_feats_cl,
+                  st, [&](auto *hdr, auto *acc, int n_log2) {
+        hipLaunchKernelGGL(sweep, dim3(zest_div_up(nvox, 64)), dim3(64), 0, st, feats_cl, proj, depth, V, D, H, W, pad, g_img_feat,
+                           g_feats_cl, hdr, acc, n_log2);
+    });
     ZEST_RETURN_LAUNCH("zest_volume_cost_bwd_det");
 }
 
@@ -252,18 +256,12 @@ extern "C" int zest_homo_warp_bwd_det(const float *proj, const float *depth, con
     ZEST_CHECK_ARG(aligned16(work), "zest_homo_warp_bwd_det: work must be 16-byte aligned");
     const long long nvox = (long long)D * Hp * Wp;
     ZEST_CHECK_ARG(nvox < (1ll << 31), "zest_homo_warp_bwd_det: %lld voxels exceed the 32-bit index range", nvox);
-    const long long n_c = nvox * 4, n = (long long)C * H * W;
+    const long long n_c = nvox * 4, n = (long long)C * H * W, ng = nvox * C;
     ZEST_CHECK_ARG(n_c <= kMaxContributions, "zest_homo_warp_bwd_det: %lld contributions (voxels x 4 taps) exceed 2^32", n_c);
     hipStream_t st = (hipStream_t)stream;
-    FixedHeader *hdr = (FixedHeader *)work;
-    unsigned long long *acc = (unsigned long long *)((char *)work + kFixedHeaderBytes);
-    (void)hipMemsetAsync(work, 0, fixed_work_bytes(n), st);
-    const int n_log2 = ceil_log2(n_c);
-    const long long ng = nvox * C;
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ng)), dim3(kThreads), 0, st, g_warped, ng, ng, ng, &hdr->max_bits[0]);
-    hipLaunchKernelGGL(homo_warp_bwd_det_kernel, dim3(zest_div_up(nvox, kThreads)), dim3(kThreads), 0, st, proj, depth,
-                       grid_in, C, D, H, W, Hp, Wp, pad, g_warped, g_src, hdr, acc, n_log2);
-    hipLaunchKernelGGL(fixed_finish_kernel, dim3(zest_div_up(n, kThreads)), dim3(kThreads), 0, st, hdr, 1, 1.0, n_log2, acc, n,
-                       g_src);
+    fixed_scatter(work, n_c, n, {{g_warped, ng, ng, ng}}, 1.0, g_src, st, [&](auto *hdr, auto *acc, int n_log2) {
+        hipLaunchKernelGGL(homo_warp_bwd_det_kernel, dim3(zest_div_up(nvox, kThreads)), dim3(kThreads), 0, st, proj, depth,
+                           grid_in, C, D, H, W, Hp, Wp, pad, g_warped, g_src, hdr, acc, n_log2);
+    });
     ZEST_RETURN_LAUNCH("zest_homo_warp_bwd_det");
 }

@@ -33,7 +33,7 @@
 // w [32,32]:  g_act[n,y,x,ci] = sum_co g w[co][ci];  g_w[co][ci] = sum_pix g[co] a[ci];  g_b[co] = sum_pix g[co].
 // 64 pixels per step in LDS; the two sums over pixels stay in registers over a workgroup's steps, one partial each,
 // added in order by the finishing launch.
-#include "costreg_conv0_grad.cuh"
+#include "mlp_engine.cuh"
 
 namespace {
 

@@ -210,6 +210,7 @@ __device__ __forceinline__ unsigned pack_pair(float lo, float hi) {
     }
 }
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return pack_pair<ZEST_PREC_BF16>(lo, hi); }
+__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)(pack_bf16(v, 0.f) & 0xFFFFu); }
 
 // the (hi, lo) registers of two values (ZEST_PREC_F16X3)
 __device__ __forceinline__ void split_pair(float a, float b, unsigned &hi, unsigned &lo) {

@@ -693,15 +693,44 @@ def costreg_apply(net, cost_vol, passes, hip_wgrad=False, hip_dgrad=False):
     return CostRegFn.apply(cost_vol.float(), net, passes, bool(hip_wgrad), bool(hip_dgrad), *params)
 
 
+def _feature_library_grads(imgs, raw, pr, low):
+    """FeatureFn.backward's gradients from the library -> (top, conv): the top layer as matrix products; a layer's
+    (g_a, g_w) from _conv_bwd on the activation of the layer below (layer 0: on the image, g_a None)."""
+    cf = lambda x: x.permute(0, 3, 1, 2)                           # [N,H,W,C] -> [N,C,H,W] (channels-last memory)
+    act = lambda i: torch.nn.functional.leaky_relu(raw[i] * pr[i][0] + pr[i][1], 0.01)
+
+    def top(g_feats, top_w):
+        g2 = g_feats.permute(0, 2, 3, 1).reshape(-1, 32).float()
+        g_top_w, g_top_b = (g2.t() @ act(-1).view(-1, 32)).view_as(top_w), g2.sum(0)
+        return (g2 @ top_w.view(32, 32).float()).view(raw[-1].shape), g_top_w, g_top_b
+
+    def conv(i, g_r, w, m):
+        x, mask = (cf(act(i - 1)) if i > 0 else imgs), [i > 0, True, False]
+        g_x, g_w = _conv_bwd(cf(g_r), x, w, low, m.stride[0], m.kernel_size[0] // 2, False, mask)
+        return (g_x.permute(0, 2, 3, 1) if i > 0 else None), g_w
+    return top, conv
+
+
+def _feature_hip_grads(imgs, raw, pr, low):
+    """... and from csrc/feature_grad.hip: zest_hip.feature_top_bwd; a layer's g_w from feature_wgrad on the kept raw output
+    and norm constants of the layer below (layer 0: the kept image), then, except for layer 0, g_a from feature_dgrad."""
+    def top(g_feats, top_w):
+        return zest_hip.feature_top_bwd(g_feats.float().contiguous(), raw[-1], pr[-1], top_w)
+
+    def conv(i, g_r, w, m):
+        x, p = (raw[i - 1], pr[i - 1]) if i > 0 else (imgs, None)
+        g_w = zest_hip.feature_wgrad(x, p, g_r, m.kernel_size[0], m.stride[0], m.in_channels)
+        return (zest_hip.feature_dgrad(g_r, w, m.stride[0], x.shape[1:3]) if i > 0 else None), g_w
+    return top, conv
+
+
 class FeatureFn(Function):
     """FeatureNet under autograd with its forward on the HIP kernels (csrc/costreg.hip, zest_conv2d_fwd), as CostRegFn:
-    norm + activation backward in HIP (zest_costreg_bn_bwd), convolution backward through aten.convolution_backward on
-    the kept raw outputs, the 1x1 top layer as matrix products.
+    one walk from the top layer down through layers 7 to 0, norm + activation backward in HIP (zest_costreg_bn_bwd), the
+    top layer's and the convolutions' gradients from the library on the kept raw outputs (_feature_library_grads).
     hip_grads (MVSNet.zest_hip_feature_grads; opt-in, holds for bf16 operands - passes == 1 - only: with passes == 3 it
-    changes nothing): the convolutions' gradients come from csrc/feature_grad.hip instead.  zest_hip.feature_top_bwd runs
-    first, then per layer from 7 to 0 zest_costreg_bn_bwd, zest_hip.feature_wgrad on the kept raw output and norm
-    constants of the layer below (the kernel forms the activation itself; layer 0 reads the kept image) and, except for
-    layer 0, zest_hip.feature_dgrad, whose channels-last fp32 result is what the next norm backward reads: no library
+    changes nothing): they come from csrc/feature_grad.hip instead (_feature_hip_grads; the kernels form the activation
+    themselves, and feature_dgrad's channels-last fp32 result is what the next norm backward reads): no library
     convolution, no cast, no layout copy, no float atomic, and fp32 results that are not rounded to bf16.  Nothing extra
     is kept between forward and backward.
     Inputs after `hip_grads`: the eight convolution weights, the top layer's weight and bias, then (weight, bias) of the
@@ -715,46 +744,16 @@ class FeatureFn(Function):
         return feats.permute(0, 3, 1, 2)
 
     @staticmethod
-    def _backward_hip(ctx, g_feats):
-        imgs, raw, pr, mo, params, _ = _kept_layers(ctx)
-        n = ctx.n
-        W, top_w, gam = params[:n], params[n], params[n + 2::2]
-        layers = ctx.net.hip_layers()
-        g_a, g_top_w, g_top_b = zest_hip.feature_top_bwd(g_feats.float().contiguous(), raw[n - 1], pr[n - 1], top_w)
-        gW, gG, gB = [None] * n, [None] * n, [None] * n
-        for i in range(n - 1, -1, -1):
-            g_r, gG[i], gB[i] = _norm_bwd(i, g_a, raw, pr, mo, gam)
-            conv = layers[i].conv
-            k, stride = conv.kernel_size[0], conv.stride[0]
-            if i > 0:
-                gW[i] = zest_hip.feature_wgrad(raw[i - 1], pr[i - 1], g_r, k, stride, conv.in_channels)
-                g_a = zest_hip.feature_dgrad(g_r, W[i], stride, raw[i - 1].shape[1:3])
-            else:
-                gW[i] = zest_hip.feature_wgrad(imgs, None, g_r, k, stride, conv.in_channels)
-        return (None, None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
-
-    @staticmethod
     def backward(ctx, g_feats):
-        if ctx.hip_grads:
-            return FeatureFn._backward_hip(ctx, g_feats)
         imgs, raw, pr, mo, params, _ = _kept_layers(ctx)
-        n, low = ctx.n, ctx.low
+        n, layers = ctx.n, ctx.net.hip_layers()
         W, top_w, gam = params[:n], params[n], params[n + 2::2]
-        layers = ctx.net.hip_layers()
-        cf = lambda x: x.permute(0, 3, 1, 2)                       # [N,H,W,C] -> [N,C,H,W] (channels-last memory)
-        act = lambda i: torch.nn.functional.leaky_relu(raw[i] * pr[i][0] + pr[i][1], 0.01)
-        g2 = g_feats.permute(0, 2, 3, 1).reshape(-1, 32).float()
-        a7 = act(n - 1).view(-1, 32)
-        g_top_w, g_top_b = (g2.t() @ a7).view_as(top_w), g2.sum(0)
-        g_a = (g2 @ top_w.view(32, 32).float()).view(raw[n - 1].shape)      # channels-last gradient of the last activation
+        top, conv = (_feature_hip_grads if ctx.hip_grads else _feature_library_grads)(imgs, raw, pr, ctx.low)
+        g_a, g_top_w, g_top_b = top(g_feats, top_w)                 # g_a: channels-last gradient of the last activation
         gW, gG, gB = [None] * n, [None] * n, [None] * n
         for i in range(n - 1, -1, -1):
             g_r, gG[i], gB[i] = _norm_bwd(i, g_a, raw, pr, mo, gam)
-            conv = layers[i].conv
-            g_x, gW[i] = _conv_bwd(cf(g_r), cf(act(i - 1)) if i > 0 else imgs, W[i], low, conv.stride[0],
-                                   conv.kernel_size[0] // 2, False, [i > 0, True, False])
-            if i > 0:
-                g_a = g_x.permute(0, 2, 3, 1)
+            g_a, gW[i] = conv(i, g_r, W[i], layers[i].conv)
         return (None, None, None, None, *gW, g_top_w, g_top_b, *(g for pair in zip(gG, gB) for g in pair))
 
 

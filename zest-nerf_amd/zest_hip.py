@@ -1112,9 +1112,47 @@ def costreg_stats(cout, device):
     return torch.empty(costreg_stat_rows(), 2, cout, device=device, dtype=torch.float64)
 
 
-def _check_stats(stats, cout, who):
-    if tuple(stats.shape) != (costreg_stat_rows(), 2, cout) or stats.dtype != torch.float64 or not stats.is_contiguous():
-        raise RuntimeError("zest_hip.%s: stats %s %s for %d channels" % (who, tuple(stats.shape), stats.dtype, cout))
+def _strict_operands(who, operands):
+    """The operands of a gradient kernel are taken as they are: each (name, tensor, layout[, test]) a contiguous fp32 tensor
+    of that layout - a shape with None for any extent, or a text with the test of rank and fixed sizes - refused in the
+    order given, before any device is looked at (the C ABI sees pointers and sizes only)."""
+    for nm, t, layout, *ok in operands:
+        fits = torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous() and all(f(t) for f in ok)
+        if fits and not isinstance(layout, str):
+            fits = t.dim() == len(layout) and all(w is None or int(w) == g for w, g in zip(layout, t.shape))
+        if not fits:
+            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s" % (
+                who, nm, layout if isinstance(layout, str) else tuple("*" if w is None else int(w) for w in layout),
+                "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous()) if torch.is_tensor(t) else type(t).__name__))
+
+
+def _strict_buffer(who, name, buf, like, size, dtype=torch.float32, aligned=False):
+    """A caller's buffer (work, out, g_vol): contiguous, of `dtype` and `size` - an element count or a shape -, 16-byte
+    aligned where asked; None: a fresh one beside `like`.  Its device is _strict_devices' business."""
+    if buf is None:
+        return torch.empty(size, device=like.device, dtype=dtype)
+    flat = isinstance(size, int)
+    if (not torch.is_tensor(buf) or buf.dtype != dtype or not buf.is_contiguous() or (aligned and buf.data_ptr() % 16)
+            or (buf.numel() != size if flat else tuple(buf.shape) != tuple(size))):
+        kind = {torch.float32: "fp32"}.get(dtype, str(dtype)[6:])
+        raise RuntimeError("%s: %s must be %s%s" % (who, name, "%d contiguous %s elements" % (size, kind) if flat else
+                                                    "a contiguous %s tensor %s" % (kind, tuple(size)), ", 16-byte aligned" * aligned))
+    return buf
+
+
+def _strict_devices(who, operands, **buffers):
+    """Last of all: every operand and every buffer is on the first operand's device, a HIP device, which is returned."""
+    dev = operands[0][1].device
+    for nm, t in [o[:2] for o in operands] + list(buffers.items()):
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (all tensors on one)" % (who, nm, t.device))
+    return dev
+
+
+def _check_stats(stats, cout, who, like):
+    if (tuple(stats.shape) != (costreg_stat_rows(), 2, cout) or stats.dtype != torch.float64 or not stats.is_contiguous()
+            or stats.device != like.device):
+        raise RuntimeError("zest_hip.%s: stats %s %s on %s for %d channels" % (who, tuple(stats.shape), stats.dtype, stats.device, cout))
 
 
 def _check_packed(w_packed, need, who, what):
@@ -1124,9 +1162,10 @@ def _check_packed(w_packed, need, who, what):
         raise RuntimeError("zest_hip.%s: packed weights of %d bytes, %s take %d" % (who, have, what, need))
 
 
-def _check_pre(pre, cin, who, name="pre"):
-    if pre is not None and (tuple(pre.shape) != (2, cin) or pre.dtype != torch.float32 or not pre.is_contiguous()):
-        raise RuntimeError("zest_hip.%s: %s %s for %d channels" % (who, name, tuple(pre.shape), cin))
+def _check_pre(pre, cin, who, like, name="pre"):
+    if pre is not None and (tuple(pre.shape) != (2, cin) or pre.dtype != torch.float32 or not pre.is_contiguous()
+                            or pre.device != like.device):
+        raise RuntimeError("zest_hip.%s: %s %s on %s for %d channels" % (who, name, tuple(pre.shape), pre.device, cin))
 
 
 def costreg_conv(x, pre, w_packed, cout, stride, passes, stats):
@@ -1135,8 +1174,8 @@ def costreg_conv(x, pre, w_packed, cout, stride, passes, stats):
     D, H, W, cin = x.shape
     _check_packed(w_packed, lib().zest_costreg_packed_bytes(cin, cout, passes), "costreg_conv",
                   "%d -> %d channels in %d passes" % (cin, cout, passes))
-    _check_pre(pre, cin, "costreg_conv")
-    _check_stats(stats, cout, "costreg_conv")
+    _check_pre(pre, cin, "costreg_conv", x)
+    _check_stats(stats, cout, "costreg_conv", x)
     o = lambda n: (n - 1) // stride + 1
     out = torch.empty(o(D), o(H), o(W), cout, device=x.device, dtype=torch.float32)
     _check(lib().zest_costreg_conv_fwd(_ptr(x), _ptr(pre), _ptr(w_packed), cin, cout, stride, passes, D, H, W,
@@ -1151,8 +1190,8 @@ def conv2d_cl(x, pre, w_packed, cout, k, stride, passes, stats):
     N, H, W, cin = x.shape
     _check_packed(w_packed, lib().zest_conv2d_packed_bytes(cin, cout, k, passes), "conv2d_cl",
                   "%d -> %d channels, k %d, %d passes" % (cin, cout, k, passes))
-    _check_pre(pre, cin, "conv2d_cl")
-    _check_stats(stats, cout, "conv2d_cl")
+    _check_pre(pre, cin, "conv2d_cl", x)
+    _check_stats(stats, cout, "conv2d_cl", x)
     o = lambda n: (n - 1) // stride + 1
     out = torch.empty(N, o(H), o(W), cout, device=x.device, dtype=torch.float32)
     _check(lib().zest_conv2d_fwd(_ptr(x), _ptr(pre), _ptr(w_packed), cin, cout, k, stride, passes, N, H, W,
@@ -1165,11 +1204,11 @@ def costreg_deconv(x0, pre0, x1, pre1, w_packed, cout, passes, stats):
     x0 = _dev(x0, "x0")
     D, H, W, cin = x0.shape
     x1 = _dev(x1, "x1", (D, H, W, cin))
-    _check_pre(pre0, cin, "costreg_deconv", "pre0")
-    _check_pre(pre1, cin, "costreg_deconv", "pre1")
+    _check_pre(pre0, cin, "costreg_deconv", x0, "pre0")
+    _check_pre(pre1, cin, "costreg_deconv", x0, "pre1")
     _check_packed(w_packed, lib().zest_costreg_deconv_packed_bytes(cin, cout, passes), "costreg_deconv",
                   "%d -> %d channels in %d passes" % (cin, cout, passes))
-    _check_stats(stats, cout, "costreg_deconv")
+    _check_stats(stats, cout, "costreg_deconv", x0)
     out = torch.empty(2 * D, 2 * H, 2 * W, cout, device=x0.device, dtype=torch.float32)
     _check(lib().zest_costreg_deconv_fwd(_ptr(x0), _ptr(pre0), _ptr(x1), _ptr(pre1), _ptr(w_packed), cin, cout, passes,
                                          D, H, W, _ptr(out), _ptr(stats), _stream(x0)), "zest_costreg_deconv_fwd")
@@ -1181,7 +1220,7 @@ def costreg_bn(stats, count, bn, batch_stats, pre, moments=None):
     batch statistics `stats` [2,C] of `count` voxels (and the running estimates updated) or from the running ones."""
     Cn = pre.shape[1]
     if batch_stats:
-        _check_stats(stats, Cn, "costreg_bn")
+        _check_stats(stats, Cn, "costreg_bn", pre)
     track = bn.running_mean is not None
     if not batch_stats and not track:
         raise RuntimeError("zest_hip.costreg_bn: a norm without running statistics needs batch statistics")
@@ -1200,6 +1239,9 @@ def costreg_bn_bwd(raw, g_act, pre, moments, gamma):
     raw, g_act = _dev(raw, "raw"), _dev(g_act, "g_act", tuple(raw.shape))
     Cn = raw.shape[-1]
     M = raw.numel() // Cn
+    ops = [("pre", pre, (2, Cn)), ("moments", moments, (2, Cn))] + ([("gamma", gamma, (Cn,))] if gamma is not None else [])
+    _strict_operands("zest_hip.costreg_bn_bwd", ops)
+    _strict_devices("zest_hip.costreg_bn_bwd", [("raw", raw)] + ops)
     stats = costreg_stats(Cn, raw.device)
     totals = torch.empty(2, Cn, device=raw.device, dtype=torch.float32)
     g_raw = torch.empty_like(raw)
@@ -1225,36 +1267,6 @@ def costreg_wgrad_work_floats(D, H, W):
     return n // 4
 
 
-def _conv0_grad_operands(who, operands, cin, same_extents=False):
-    """The checks costreg_wgrad and costreg_dgrad share.  operands: two of (name, tensor, layout as text, test of rank and
-    fixed sizes).  dtype, layout and shapes first (the C ABI sees pointers and sizes only), then the device - the first
-    operand's, which is returned.  same_extents: the two agree in their three leading sizes."""
-    for nm, t, what, ok in operands:
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
-            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
-                               % (who, nm, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
-                                  if torch.is_tensor(t) else type(t).__name__))
-    (nm0, t0), (nm1, t1) = operands[0][:2], operands[1][:2]
-    if same_extents and tuple(t1.shape[:3]) != tuple(t0.shape[:3]):
-        raise RuntimeError("%s: %s %s against %s %s" % (who, nm1, tuple(t1.shape), nm0, tuple(t0.shape)))
-    if not 1 <= cin <= COST_CL_CHANNELS:
-        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
-    for nm, t in ((nm0, t0), (nm1, t1)):
-        if not t.is_cuda or t.device != t0.device:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (both tensors on one)" % (who, nm, t.device))
-    return t0.device
-
-
-def _conv0_grad_out(who, out, shape, device):
-    """The caller's result buffer, checked, or a fresh one."""
-    if out is None:
-        return torch.empty(shape, device=device, dtype=torch.float32)
-    if (not torch.is_tensor(out) or out.device != device or out.dtype != torch.float32 or not out.is_contiguous()
-            or tuple(out.shape) != shape):
-        raise RuntimeError("%s: out must be a contiguous fp32 tensor %s on %s" % (who, shape, device))
-    return out
-
-
 def costreg_wgrad(x_cl, g_cl, cin, work=None, out=None):
     """Weight gradient of CostRegNet.conv0: x_cl [D,H,W,48] (the padded channels-last cost volume of the forward; channels
     from `cin` on are not read into the result), g_cl [D,H,W,8] (costreg_bn_bwd's g_raw) -> g_w [8,cin,3,3,3] fp32.
@@ -1262,15 +1274,16 @@ def costreg_wgrad(x_cl, g_cl, cin, work=None, out=None):
     fp32 elements, 16-byte aligned; [8,cin,3,3,3]) instead of fresh ones."""
     who, cin = "zest_hip.costreg_wgrad", int(cin)
     cl = lambda ch: ("[D,H,W,%d]" % ch, lambda t: t.dim() == 4 and t.shape[3] == ch)
-    dev = _conv0_grad_operands(who, (("x_cl", x_cl) + cl(COST_CL_CHANNELS), ("g_cl", g_cl) + cl(8)), cin, same_extents=True)
+    ops = (("x_cl", x_cl) + cl(COST_CL_CHANNELS), ("g_cl", g_cl) + cl(8))
+    _strict_operands(who, ops)
+    if tuple(g_cl.shape[:3]) != tuple(x_cl.shape[:3]):
+        raise RuntimeError("%s: g_cl %s against x_cl %s" % (who, tuple(g_cl.shape), tuple(x_cl.shape)))
+    if not 1 <= cin <= COST_CL_CHANNELS:
+        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
     D, H, W, _ = x_cl.shape
-    need = costreg_wgrad_work_floats(D, H, W)
-    if work is None:
-        work = torch.empty(need, device=dev, dtype=torch.float32)
-    elif (work.device != dev or work.dtype != torch.float32 or not work.is_contiguous() or work.numel() != need
-          or work.data_ptr() % 16):
-        raise RuntimeError("%s: work must be %d contiguous fp32 elements on %s, 16-byte aligned" % (who, need, dev))
-    out = _conv0_grad_out(who, out, (8, cin, 3, 3, 3), dev)
+    work = _strict_buffer(who, "work", work, x_cl, costreg_wgrad_work_floats(D, H, W), aligned=True)
+    out = _strict_buffer(who, "out", out, x_cl, (8, cin, 3, 3, 3))
+    _strict_devices(who, ops, work=work, out=out)
     _check(lib().zest_costreg_wgrad(_ptr(x_cl), _ptr(g_cl), D, H, W, cin, 8, _ptr(work), _ptr(out), _stream(x_cl)),
            "zest_costreg_wgrad")
     return out
@@ -1291,30 +1304,20 @@ def costreg_dgrad(g_cl, weight, out=None):
     own, cin 1 .. 48) -> g_x [cin,D,H,W] fp32 channel planes.  bf16-rounded operands, fp32 accumulation, every element
     written once, no atomics.  out: the caller's [cin,D,H,W] buffer instead of a fresh one."""
     who = "zest_hip.costreg_dgrad"
-    operands = (("g_cl", g_cl, "[D,H,W,8]", lambda t: t.dim() == 4 and t.shape[3] == 8),
-                ("weight", weight, "[8,cin,3,3,3]", lambda t: t.dim() == 5 and t.shape[0] == 8 and tuple(t.shape[2:]) == (3, 3, 3)))
-    cin = int(weight.shape[1]) if torch.is_tensor(weight) and weight.dim() == 5 else 0    # anything else is refused before cin is looked at
-    dev = _conv0_grad_operands(who, operands, cin)
-    D, H, W, _ = g_cl.shape
-    out = _conv0_grad_out(who, out, (cin, D, H, W), dev)
+    ops = (("g_cl", g_cl, "[D,H,W,8]", lambda t: t.dim() == 4 and t.shape[3] == 8),
+           ("weight", weight, "[8,cin,3,3,3]", lambda t: t.dim() == 5 and t.shape[0] == 8 and tuple(t.shape[2:]) == (3, 3, 3)))
+    _strict_operands(who, ops)
+    (D, H, W, _), cin = g_cl.shape, int(weight.shape[1])
+    if not 1 <= cin <= COST_CL_CHANNELS:
+        raise RuntimeError("%s: cin %d, expected 1 .. %d" % (who, cin, COST_CL_CHANNELS))
+    out = _strict_buffer(who, "out", out, g_cl, (cin, D, H, W))
+    _strict_devices(who, ops, out=out)
     _check(lib().zest_costreg_dgrad(_ptr(g_cl), _ptr(weight), D, H, W, cin, 8, _ptr(out), _stream(g_cl)),
            "zest_costreg_dgrad")
     return out
 
 
 # ------------------------------------------------------------------ gradients of the feature pyramid (csrc/feature_grad.hip)
-def _feature_operand(who, name, t, what, ok, device=None):
-    """One operand of the pyramid's gradient kernels: a contiguous fp32 tensor of the stated layout on a HIP device
-    (`device`: the one an earlier operand is on).  dtype, layout and shape first: the C ABI sees pointers and sizes only."""
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not ok(t):
-        raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s"
-                           % (who, name, what, "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous())
-                              if torch.is_tensor(t) else type(t).__name__))
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (all tensors on one)" % (who, name, t.device))
-    return t.device
-
-
 def _conv_out(n, stride):
     return (n - 1) // stride + 1
 
@@ -1335,22 +1338,25 @@ def feature_wgrad(x, pre, g, k, stride, cin):
     itself; with pre None: x [N,cin,Hi,Wi] is the layer's input as it is (the image, channel planes).  bf16-rounded
     operands, fp32 accumulation, fp32 result, no atomics: the same bits on every call."""
     who, cin, k, stride = "zest_hip.feature_wgrad", int(cin), int(k), int(stride)
+    if stride < 1:
+        raise RuntimeError("%s: stride %d" % (who, stride))
     if pre is None:
-        dev = _feature_operand(who, "x", x, "[N,%d,Hi,Wi] (pre is None: the layer's own input)" % cin,
-                               lambda t: t.dim() == 4 and t.shape[1] == cin)
+        ops = [("x", x, "[N,%d,Hi,Wi] (pre is None: the layer's own input)" % cin, lambda t: t.dim() == 4 and t.shape[1] == cin)]
+        _strict_operands(who, ops)
         N, _, Hi, Wi = x.shape
         strides = (cin * Hi * Wi, Wi, 1, Hi * Wi)
     else:
-        dev = _feature_operand(who, "x", x, "[N,Hi,Wi,%d]" % cin, lambda t: t.dim() == 4 and t.shape[3] == cin)
+        ops = [("x", x, "[N,Hi,Wi,%d]" % cin, lambda t: t.dim() == 4 and t.shape[3] == cin),
+               ("pre", pre, "[2,%d]" % cin, lambda t: tuple(t.shape) == (2, cin))]
+        _strict_operands(who, ops)
         N, Hi, Wi, _ = x.shape
         strides = (Hi * Wi * cin, Wi * cin, cin, 1)
-        _feature_operand(who, "pre", pre, "[2,%d]" % cin, lambda t: tuple(t.shape) == (2, cin), dev)
-    if stride < 1:
-        raise RuntimeError("%s: stride %d" % (who, stride))
     Ho, Wo = _conv_out(Hi, stride), _conv_out(Wi, stride)
-    _feature_operand(who, "g", g, "[%d,%d,%d,cout]" % (N, Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[:3]) == (N, Ho, Wo), dev)
+    ops.append(("g", g, "[%d,%d,%d,cout]" % (N, Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[:3]) == (N, Ho, Wo)))
+    _strict_operands(who, ops[-1:])
     cout = int(g.shape[3])
     need = feature_wgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride)[3]      # refuses a layer shape without a kernel
+    dev = _strict_devices(who, ops)
     work = torch.empty(need, device=dev, dtype=torch.float32)
     out = torch.empty(cout, cin, k, k, device=dev, dtype=torch.float32)
     _check(lib().zest_feature_wgrad(_ptr(x), *strides, _ptr(pre), _ptr(g), N, Hi, Wi, cin, cout, k, stride, _ptr(work), _ptr(out),
@@ -1378,11 +1384,14 @@ def feature_dgrad(g, w, stride, in_hw):
     if stride < 1 or Hi < 1 or Wi < 1:
         raise RuntimeError("%s: stride %d, input extents %d x %d" % (who, stride, Hi, Wi))
     Ho, Wo = _conv_out(Hi, stride), _conv_out(Wi, stride)
-    dev = _feature_operand(who, "g", g, "[N,%d,%d,cout]" % (Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[1:3]) == (Ho, Wo))
+    ops = [("g", g, "[N,%d,%d,cout]" % (Ho, Wo), lambda t: t.dim() == 4 and tuple(t.shape[1:3]) == (Ho, Wo))]
+    _strict_operands(who, ops)
     N, cout = int(g.shape[0]), int(g.shape[3])
-    _feature_operand(who, "w", w, "[%d,cin,k,k]" % cout, lambda t: t.dim() == 4 and t.shape[0] == cout and t.shape[2] == t.shape[3], dev)
+    ops.append(("w", w, "[%d,cin,k,k]" % cout, lambda t: t.dim() == 4 and t.shape[0] == cout and t.shape[2] == t.shape[3]))
+    _strict_operands(who, ops[-1:])
     cin, k = int(w.shape[1]), int(w.shape[2])
     nbytes = feature_dgrad_launch_shape(N, Hi, Wi, cin, cout, k, stride)[2]    # refuses a layer shape without a kernel
+    dev = _strict_devices(who, ops)
     wpack = torch.empty(nbytes // 2, device=dev, dtype=torch.int16)
     out = torch.empty(N, Hi, Wi, cin, device=dev, dtype=torch.float32)
     _check(lib().zest_feature_dgrad(_ptr(g), _ptr(w), N, Hi, Wi, cin, cout, k, stride, _ptr(wpack), _ptr(out), _stream(g)),
@@ -1404,11 +1413,14 @@ def feature_top_bwd(g_feats, raw, pre, top_w):
     and pre [2,32] of the last 3 x 3 layer, top_w [32,32,1,1] -> (g_act [N,h,w,32] channels-last, g_top_w like top_w,
     g_top_b [32]).  The two sums over pixels are added in a fixed order: the same bits on every call."""
     who = "zest_hip.feature_top_bwd"
-    dev = _feature_operand(who, "g_feats", g_feats, "[N,32,h,w]", lambda t: t.dim() == 4 and t.shape[1] == 32)
+    ops = [("g_feats", g_feats, "[N,32,h,w]", lambda t: t.dim() == 4 and t.shape[1] == 32)]
+    _strict_operands(who, ops)
     N, _, h, w = g_feats.shape
-    _feature_operand(who, "raw", raw, "[%d,%d,%d,32]" % (N, h, w), lambda t: tuple(t.shape) == (N, h, w, 32), dev)
-    _feature_operand(who, "pre", pre, "[2,32]", lambda t: tuple(t.shape) == (2, 32), dev)
-    _feature_operand(who, "top_w", top_w, "[32,32,1,1]", lambda t: tuple(t.shape) in ((32, 32, 1, 1), (32, 32)), dev)
+    ops += [("raw", raw, "[%d,%d,%d,32]" % (N, h, w), lambda t: tuple(t.shape) == (N, h, w, 32)),
+            ("pre", pre, "[2,32]", lambda t: tuple(t.shape) == (2, 32)),
+            ("top_w", top_w, "[32,32,1,1]", lambda t: tuple(t.shape) in ((32, 32, 1, 1), (32, 32)))]
+    _strict_operands(who, ops[1:])
+    dev = _strict_devices(who, ops)
     work = torch.empty(feature_top_bwd_launch_shape(N, h, w)[2], device=dev, dtype=torch.float32)
     g_act = torch.empty(N, h, w, 32, device=dev, dtype=torch.float32)
     g_w, g_b = torch.empty_like(top_w), torch.empty(32, device=dev, dtype=torch.float32)
@@ -1422,8 +1434,11 @@ def costreg_out(raw_a, pre_a, raw_b, pre_b):
     raw_a = _dev(raw_a, "raw_a")
     D, H, W, Cn = raw_a.shape
     raw_b = _dev(raw_b, "raw_b", (D, H, W, 8))
-    if Cn != 8 or tuple(pre_a.shape) != (2, 8) or tuple(pre_b.shape) != (2, 8):
-        raise RuntimeError("zest_hip.costreg_out: %s, %s, %s" % (tuple(raw_a.shape), tuple(pre_a.shape), tuple(pre_b.shape)))
+    if Cn != 8:
+        raise RuntimeError("zest_hip.costreg_out: raw_a %s, expected 8 channels" % (tuple(raw_a.shape),))
+    ops = [("pre_a", pre_a, (2, 8)), ("pre_b", pre_b, (2, 8))]
+    _strict_operands("zest_hip.costreg_out", ops)
+    _strict_devices("zest_hip.costreg_out", [("raw_a", raw_a)] + ops)
     out = torch.empty(1, 8, D, H, W, device=raw_a.device, dtype=torch.float32)
     _check(lib().zest_costreg_out(_ptr(raw_a), _ptr(pre_a), _ptr(raw_b), _ptr(pre_b), D, H, W, _ptr(out),
                                   _stream(raw_a)), "zest_costreg_out")
@@ -1434,34 +1449,17 @@ def costreg_out(raw_a, pre_a, raw_b, pre_b):
 DET_MAX_CONTRIBUTIONS = 1 << 32
 
 
-def _det_operands(who, operands):
-    """The *_det calls take their operands as they are - (name, tensor, shape with None for any extent): contiguous fp32
-    tensors of those shapes, checked before the device (the C ABI sees pointers and sizes only) - and then on one HIP
-    device, which is returned."""
-    for nm, t, shape in operands:
-        if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != len(shape)
-                or any(w is not None and int(w) != g for w, g in zip(shape, t.shape))):
-            raise RuntimeError("%s: %s must be a contiguous fp32 tensor %s, got %s" % (
-                who, nm, tuple("*" if w is None else int(w) for w in shape),
-                "%s %s, contiguous: %s" % (t.dtype, tuple(t.shape), t.is_contiguous()) if torch.is_tensor(t) else type(t).__name__))
-    return operands[0][1].device
-
-
 def _det_checked(who, operands, work, nbytes, n_contrib, what):
-    """Operands, workspace and the number of contributions of a *_det call, every refusal before the device is looked at.
-    -> the workspace (the caller's, or a fresh one)."""
-    dev = _det_operands(who, operands)
+    """Operands - (name, tensor, shape with None for any extent) -, the number of contributions and the workspace of a *_det
+    call, every refusal before the device is looked at.  -> the workspace (the caller's, or a fresh one)."""
+    _strict_operands(who, operands)
     if nbytes == 0:
         _check(1, who)
-    if work is not None and (not torch.is_tensor(work) or work.dtype != torch.uint8 or not work.is_contiguous()
-                             or work.numel() != nbytes or work.data_ptr() % 16):
-        raise RuntimeError("%s: work must be %d contiguous uint8 elements, 16-byte aligned" % (who, nbytes))
     if n_contrib > DET_MAX_CONTRIBUTIONS:
         raise RuntimeError("%s: %d contributions (%s) exceed 2^32" % (who, n_contrib, what))
-    for nm, t in [(o[0], o[1]) for o in operands] + ([("work", work)] if work is not None else []):
-        if not t.is_cuda or t.device != dev:
-            raise RuntimeError("%s: %s is on %s; this path runs only on a HIP device (all tensors on one)" % (who, nm, t.device))
-    return torch.empty(nbytes, device=dev, dtype=torch.uint8) if work is None else work
+    work = _strict_buffer(who, "work", work, operands[0][1], nbytes, torch.uint8, aligned=True)
+    _strict_devices(who, operands, work=work)
+    return work
 
 
 def volume_cost_bwd(feats_cl, proj, depth, pad, g_img_feat, deterministic=False, work=None):

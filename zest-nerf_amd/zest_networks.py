@@ -681,6 +681,24 @@ class MVSNet(nn.Module):
     regularisation.  Constructor, attribute names and state-dict keys follow the reference
     (networks.py:1061-1238)."""
 
+    # The switches of the training path, name -> default; each is a class attribute too (below the class), so forward
+    # reads plain attributes.  _Generator._volume sets them from the arguments of the same names (absent or None: left
+    # alone).  All but the first are opt-in; the three zest_hip_*grad* hold under bf16 autocast (--precision 16) only.
+    ZEST_SWITCHES = {
+        # both nets' training forward on the HIP kernels (FeatureFn, CostRegFn); None: decided per call - under bf16 autocast
+        "zest_hip_costreg_train": None,
+        # cost_reg_2.conv0's weight gradient in HIP (CostRegFn keeps a [D,H,W,48] fp32 cost volume: 0.5 GB at 128 x 120 x 176)
+        "zest_hip_costreg_wgrad": False,
+        # cost_reg_2.conv0's data gradient - towards the cost volume - in HIP, fp32 channel planes (nothing extra is kept)
+        "zest_hip_costreg_dgrad": False,
+        # the feature pyramid's convolution gradients - weight, data, 1 x 1 top layer - in HIP (csrc/feature_grad.hip, FeatureFn)
+        "zest_hip_feature_grads": False,
+        # (also ZEST_DETERMINISTIC=1, see deterministic_choice) the order-independent plane-sweep backward, no float atomics
+        "zest_deterministic": False,
+    }
+    # no argument sets this one: False keeps the whole-image evaluation (hip_path) on the library modules
+    zest_hip_costreg = True
+
     def __init__(self, num_groups=1, norm_act=ActivatedBatchNorm, levels=1):
         super().__init__()
         self.levels = levels
@@ -689,20 +707,6 @@ class MVSNet(nn.Module):
         self.feature = FeatureNet()
         self.chunk = 1024
         self.cost_reg_2 = CostRegNet(32 + 9, norm_act)
-        # opt-in: under autograd in bf16 (--precision 16) the weight gradient of cost_reg_2.conv0 from the HIP kernel
-        # (zest_autograd.CostRegFn; keeps a [D,H,W,48] fp32 copy of the cost volume, 0.5 GB at 128 x 120 x 176, until
-        # the backward pass).  No effect in fp32 mode.
-        self.zest_hip_costreg_wgrad = False
-        # opt-in, likewise: the data gradient of cost_reg_2.conv0 - the gradient towards the cost volume - from the HIP
-        # kernel, as fp32 channel planes (nothing extra is kept for it).  No effect in fp32 mode.
-        self.zest_hip_costreg_dgrad = False
-        # opt-in, likewise: the gradients of the feature pyramid's convolutions - weight, data and the 1 x 1 top layer -
-        # from the HIP kernels of csrc/feature_grad.hip (zest_autograd.FeatureFn; nothing extra is kept).  No effect in
-        # fp32 mode.
-        self.zest_hip_feature_grads = False
-        # opt-in (args.zest_deterministic / ZEST_DETERMINISTIC=1, see deterministic_choice): the gradient towards the
-        # feature maps through the order-independent plane-sweep backward instead of float atomics
-        self.zest_deterministic = False
 
     def build_volume_cost(self, imgs, feats, proj_mats, depth_values, pad=0):
         """imgs [1,V,3,Hi,Wi]; feats [1,V,32,H,W]; proj_mats [1,V,3,4]; depth_values [1,D]
@@ -718,8 +722,7 @@ class MVSNet(nn.Module):
         if torch.is_grad_enabled() and feats.requires_grad:
             import zest_autograd
             img_feat, masks = zest_autograd.VolumeCostFn.apply(feats[0].float(), imgs_lr.detach(), proj_mats[0, 1:].detach(),
-                                                               depth.detach(), pad,
-                                                               bool(getattr(self, "zest_deterministic", False)))
+                                                               depth.detach(), pad, bool(self.zest_deterministic))
         else:
             img_feat, masks = zest_hip.volume_cost(feats[0], imgs_lr, proj_mats[0, 1:], depth, pad)
         return img_feat[None], masks[None]
@@ -731,7 +734,7 @@ class MVSNet(nn.Module):
         half = lambda n: (n - 1) // 2 + 1
         Hf, Wf = half(half(H)), half(half(W))
         return (not torch.is_grad_enabled() and imgs.is_cuda and B == 1 and 3 * V + 32 <= zest_hip.COST_CL_CHANNELS
-                and not ((Hf + 2 * pad) % 8 or (Wf + 2 * pad) % 8) and getattr(self, "zest_hip_costreg", True)
+                and not ((Hf + 2 * pad) % 8 or (Wf + 2 * pad) % 8) and self.zest_hip_costreg
                 and self.cost_reg_2.hip_supported())
 
     def forward(self, imgs, proj_mats, near_far, pad=0, return_color=False, lindisp=False,
@@ -749,8 +752,8 @@ class MVSNet(nn.Module):
         hip = not return_color and self.hip_path(imgs, pad)
         passes = 1 if torch.is_autocast_enabled() else 3
         feats_cl = None
-        hip_train = getattr(self, "zest_hip_costreg_train", None)
-        hip_train = (torch.is_autocast_enabled() if hip_train is None else bool(hip_train)) and torch.is_grad_enabled() and imgs.is_cuda
+        hip_train = torch.is_autocast_enabled() if self.zest_hip_costreg_train is None else bool(self.zest_hip_costreg_train)
+        hip_train = hip_train and torch.is_grad_enabled() and imgs.is_cuda
         if hip and self.feature.hip_supported():
             feats_cl = self.feature.forward_hip(imgs[0], passes)
             feats = feats_cl.permute(0, 3, 1, 2)[None]
@@ -758,8 +761,7 @@ class MVSNet(nn.Module):
               and all(m.training for m in self.feature.modules() if isinstance(m, ActivatedBatchNorm))):
             import zest_autograd                      # the pyramid's forward on the HIP kernels under autograd (FeatureFn)
             # zest_hip_feature_grads (opt-in, --precision 16 only): the convolutions' gradients in HIP as well
-            feats = zest_autograd.feature_apply(self.feature, imgs[0], passes,
-                                                hip_grads=bool(getattr(self, "zest_hip_feature_grads", False)))[None]
+            feats = zest_autograd.feature_apply(self.feature, imgs[0], passes, hip_grads=bool(self.zest_hip_feature_grads))[None]
         else:
             feats, _ = self.feature(imgs.reshape(B * V, 3, H, W))
             feats = feats.view(B, V, *feats.shape[1:])
@@ -790,13 +792,16 @@ class MVSNet(nn.Module):
             import zest_autograd
             # zest_hip_costreg_wgrad (opt-in, --precision 16 only): the first layer's weight gradient in HIP as well;
             # zest_hip_costreg_dgrad (likewise): its data gradient
-            volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes,
-                                                      hip_wgrad=bool(getattr(self, "zest_hip_costreg_wgrad", False)),
-                                                      hip_dgrad=bool(getattr(self, "zest_hip_costreg_dgrad", False)))
+            volume_feat = zest_autograd.costreg_apply(self.cost_reg_2, cost_vol, passes, hip_wgrad=bool(self.zest_hip_costreg_wgrad),
+                                                      hip_dgrad=bool(self.zest_hip_costreg_dgrad))
         else:
             volume_feat, _ = self.cost_reg_2(cost_vol)
         volume_feat = volume_feat.reshape(1, -1, *volume_feat.shape[2:])
         return volume_feat, feats, depth_values
+
+
+for _name, _default in MVSNet.ZEST_SWITCHES.items():
+    setattr(MVSNet, _name, _default)
 
 
 # ------------------------------------------------------------------------------------------
@@ -832,12 +837,12 @@ class _Generator(nn.Module):
             if (not train and getattr(self.args, "zest_graph_builders", True) and isinstance(net, MVSNet)
                     and net.feature.hip_supported() and net.hip_path(imgs, self.args.pad)):
                 return self._volume_replayed(net, imgs, proj_mats, near_far)
-            for name in ("zest_hip_costreg_train", "zest_hip_costreg_wgrad", "zest_hip_costreg_dgrad", "zest_hip_feature_grads",
-                         "zest_deterministic"):
-                if train and isinstance(net, MVSNet) and getattr(self.args, name, None) is not None:
-                    setattr(net, name, bool(getattr(self.args, name)))      # the caller's choice, else MVSNet's default
-            if train and isinstance(net, MVSNet) and os.environ.get("ZEST_DETERMINISTIC", ""):
-                net.zest_deterministic = deterministic_choice(self.args)    # the environment overrides the argument
+            if train and isinstance(net, MVSNet):
+                for name in MVSNet.ZEST_SWITCHES:
+                    if getattr(self.args, name, None) is not None:
+                        setattr(net, name, bool(getattr(self.args, name)))  # the caller's choice, else the builder's own
+                if os.environ.get("ZEST_DETERMINISTIC", ""):
+                    net.zest_deterministic = deterministic_choice(self.args)    # the environment overrides the argument
             return net(imgs, proj_mats, near_far, pad=self.args.pad)[0].float()
 
     def _volume_replayed(self, net, imgs, proj_mats, near_far):
@@ -855,7 +860,7 @@ class _Generator(nn.Module):
         params = weights + list(net.buffers())
         norms = tuple((m.training, m.eps, m.momentum) for m in net.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm))
         key = (tuple(imgs.shape), tuple(proj_mats.shape), imgs.dtype, self.args.pad, torch.is_autocast_enabled(), norms,
-               str(imgs.device), getattr(net, "zest_hip_costreg", True), tuple(p._version for p in weights),
+               str(imgs.device), net.zest_hip_costreg, tuple(p._version for p in weights),
                tuple(p.data_ptr() for p in params))
         graphs = self.__dict__.setdefault("_zest_builder_graphs", {})
         for k in [k for k, e in graphs.items() if e["net"]() is None]:
